@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: drone-steps/sec of the fused (trajectory -> geometric controller
 -> mixer -> physics step -> observation) kernel, plus the achieved algorithmic HBM bandwidth
-against the MI355X roofline and a CPU baseline (the float64 oracle) timed in the same run.
+against the MI355X roofline; with --full also a CPU baseline (the float64 oracle) and the
+secondary measurements (other launch forms, sizes, precisions and workloads) in the same run.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`ms_per_step`: wall-clock
+milliseconds per timed step).  --dump-outputs DIR writes what the timed call returned for its last
+step as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs run to run).
 
 N > 1: one process per GPU.  Launched under torch.distributed.run (RANK / WORLD_SIZE in the environment) it is one rank;
 launched plainly it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child BEFORE anything
@@ -349,6 +354,33 @@ def _timed_steps(device, fn, steps):
     return e0.elapsed_time(e1) * 1e3 / steps
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000        # --dump-outputs: at most this many bytes of .npy payload in all
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each named array as out_dir/<name>.npy, float64 if it is float64 on the device and float32 otherwise.
+    Per-drone arrays are [..., row] with the drones on the leading axes; 1-D arrays (per env) are small and always written whole.  If
+    everything together exceeds `budget`, the same fixed, seeded sample of drone rows is taken from every per-drone array (flattened
+    to [n, row], rows in ascending order) and the row indices are written beside them as sample_rows.npy: the sample depends only
+    on the drone count and the budget, so two runs with the same arguments dump the same rows."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > budget:
+        rowed = [k for k, a in host.items() if a.ndim >= 2]
+        n = int(np.prod(host[rowed[0]].shape[:-1]))
+        if any(int(np.prod(host[k].shape[:-1])) != n for k in rowed):
+            raise SystemExit("bench.py: --dump-outputs: the per-drone arrays do not share the drone axis")
+        small = total - sum(host[k].nbytes for k in rowed)
+        keep = max(1, min(n, int((budget - small - 4096) // ((total - small) / n + 8))))     # + 8 B per row (its index), 4 kB for .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host.update({k: np.ascontiguousarray(host[k].reshape(n, -1)[rows]) for k in rowed})
+        host["sample_rows"] = rows.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def _pmc_traffic(name, drones_per_launch):
     """HBM-side bytes per launch from the committed summary of the separate rocprofv3 --pmc passes (profiles/), scaled to the
     launch shape actually used: the passes count per launch of `drones_per_launch_counted` drones and traffic is per drone."""
@@ -688,8 +720,14 @@ def main(argv=None):
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--dtype", default="float32", choices=["float32", "float64", "float16", "float32c"])
     ap.add_argument("--integrator", default="euler", choices=["euler", "rk4"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract's line: skip the secondary measurements (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (other launch forms, sizes, precisions and workloads, the copy ceiling) and the CPU "
+                         "baselines after the timed steps; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy (float32, or float64 for "
+                         "--dtype float64; a fixed seeded sample of drone rows beyond 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (profiling runs)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--fused-rollout", type=int, default=0, metavar="T",
                     help="run the steps as launches of T control steps each (mds_rollout_geometric_fused: state in registers, "
@@ -731,6 +769,8 @@ def main(argv=None):
     ap.add_argument("--gather-obs", action="store_true",
                     help="after the timed region, also time the optional whole-swarm observation all-gather (RCCL over xGMI); never part of `value`")
     args = ap.parse_args(argv)
+    if not args.full:                       # a plain run: the headline line only
+        args.no_extras = args.no_cpu_baseline = True
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus, argv)
     # c5 flies open loop (random RPM around hover, no controller): under the explicit-Euler model the body rates blow up after ~1500
@@ -969,6 +1009,10 @@ def main(argv=None):
 
     obs = c5_log[(c5_k[0] - 1) % c5_T] if c5 else env._obs
     ok = bool(torch.isfinite(obs).all().item()) and abs(float(obs[..., 3:7].norm(dim=-1).mean().item()) - 1.0) < 1e-3
+    if args.dump_outputs and rank == 0:
+        # what the timed call hands its caller for the last step: the [E, D, 20] observation (c5: the log slot that step wrote),
+        # and on c4 the per-env QP status beside it
+        dump_outputs(args.dump_outputs, dict(obs=obs.reshape(E, D, 20), **({"cbf_status": env._cbf_status} if c4 else {})))
     n_local = E * D
     total_units = n_local * world * args.steps
     value = total_units / elapsed

@@ -3,8 +3,8 @@ O=gpurun_out/r04f2
 mkdir -p $O
 t0=$(date +%s); timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; echo "pytest rc $? in $(( $(date +%s) - t0 )) s"; tail -2 $O/pytest_gpu.log
 t0=$(date +%s); timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $? in $(( $(date +%s) - t0 )) s"; tail -3 $O/smoke.log
-t0=$(date +%s); timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver bench rc $? in $(( $(date +%s) - t0 )) s"
-t0=$(date +%s); timeout -k 10 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc $? in $(( $(date +%s) - t0 )) s"
+t0=$(date +%s); timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver bench rc $? in $(( $(date +%s) - t0 )) s"
+t0=$(date +%s); timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc $? in $(( $(date +%s) - t0 )) s"
 python3 - <<'PY'
 import json
 for n in ("driver", "default"):

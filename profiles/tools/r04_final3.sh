@@ -4,8 +4,8 @@ O=gpurun_out/r04f3
 mkdir -p $O
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -4 $O/pytest_gpu.log
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?"; tail -4 $O/smoke.log
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver bench rc $?"
-timeout -k 10 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc $?"
+timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver bench rc $?"
+timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default bench rc $?"
 timeout -k 10 300 python3 bench.py --scaling strong --shard-of 8 --no-cpu-baseline --no-extras > $O/bench_shard8.json 2> $O/bench_shard8.err; echo "shard bench rc $?"
 python3 - <<'PY'
 import json

@@ -157,3 +157,32 @@ def test_shard_inputs_slices_and_refuses_a_ragged_partition():
         bench.shard_inputs(64, 8, "c3", 0, 3, "strong")
     w = bench.shard_inputs(16, 8, "c3", 1, 2, "weak")
     np.testing.assert_array_equal(w[2], bench.make_inputs(16, 8, "c3", 1001)[2])
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: an output under the budget is written whole (float32 / float64 kept apart); above it every per-drone array keeps
+    the same seeded sample of rows, named in sample_rows.npy, the per-env status whole -- the same rows on every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    g = torch.Generator().manual_seed(0)
+    obs = torch.randn((64, 8, 20), generator=g, dtype=torch.float16)
+    bench.dump_outputs(str(tmp_path / "a"), {"obs": obs})
+    a = np.load(tmp_path / "a" / "obs.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["obs.npy"] and a.dtype == np.float32 and a.shape == (64, 8, 20)
+    np.testing.assert_array_equal(a, obs.float().numpy())
+    obs = torch.randn((64, 8, 20), generator=g, dtype=torch.float64)
+    st = torch.arange(64, dtype=torch.int32)
+    budget = 40000
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"obs": obs, "cbf_status": st}, budget=budget)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["cbf_status.npy", "obs.npy", "sample_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= budget
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    b = np.load(tmp_path / "b" / "obs.npy")
+    assert b.dtype == np.float64 and 0 < len(rows) < 512 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(b, obs.numpy().reshape(512, 20)[rows.astype(int)])
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "cbf_status.npy"), np.arange(64, dtype=np.float32))
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))

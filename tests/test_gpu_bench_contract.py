@@ -5,15 +5,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_driver_command_prints_the_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extras",
-                          "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+def test_driver_command_prints_the_contract_line(tmp_path):
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                          "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                     # ONE JSON line
@@ -38,6 +40,14 @@ def test_driver_command_prints_the_contract_line():
     assert rf["traffic"] is not None and 0.15 < rf["traffic"] / rf["bytes_per_launch"] < 1.02 and 0.3 < rf["valu"]["frac_of_issue_rate"] < 1.0
     assert rf["frac"] > 0.4 and r["value"] > 3.5e10            # committed: 0.57-0.61, 4.8-5.7e10
     assert r["state_sane"] is True and r["ranks_seen"] == 1
+    # a plain run is the headline alone: the secondary measurements and the CPU baselines only run with --full
+    assert r["cpu_baseline"] is None and not {"per_step", "fused_rollout", "compare_models", "configs_1_c2", "configs_4_c4", "configs_5_c5",
+                                               "rk4", "f64", "f32c"} & set(r) and "copy_ceiling" not in rf and "hbm_resident" not in rf
+    # --dump-outputs: the observation the timed call returned for its last step, every drone of the shard
+    assert sorted(os.listdir(dump)) == ["obs.npy"]
+    obs = np.load(dump / "obs.npy")
+    assert obs.shape == (65536, 8, 20) and obs.dtype == np.float32 and np.isfinite(obs).all()
+    assert np.abs(np.linalg.norm(obs[..., 3:7], axis=-1) - 1).max() < 1e-3
 
 
 def test_strong_scaling_shard_line():
