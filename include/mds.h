@@ -499,6 +499,41 @@ int mds_step_nominal(mds_handle* h, double t, void* obs_dev, void* action_dev, v
  * [n_steps, n, 20] or NULL; obs_dev [n,20] holds the current observation on entry and the last one on return. */
 int mds_rollout_nominal_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_dev, void* stream);
 
+/* ---- FedCE system identification and the decentralised LQR (control/dlqr, simulations/EnvGeometric.py fedCE) ----
+ * Per drone the handle keeps the RLS state of DecentralizedLQR.approx_theta_update in float64 in every dtype: P [16,16] and the
+ * 12 free entries of theta = [A^T; B^T] [16,12] (project_theta: A[6,1], A[7,0], B[3:6,1:4] row-major, B[8,0]; A[0:3,3:6] =
+ * A[9:12,6:9] = I; all else 0).  Drone i = env * num_drones + j.  DYN / DYN_DRAG physics, Euler, f32 / f64 storage and
+ * 1 <= num_drones <= 16 only: MDS_EUNSUPPORTED otherwise (fp16 storage, MDS_F32C, RK4, ground effect / downwash, more drones).
+ * Every drone starts from the same theta / P (mds_fedce_init), and the second pred_errors entry is taken against the true hover
+ * model of the handle's constants (A[6,1] = G, A[7,0] = -G, B[3:6,1:4] = J^-1, B[8,0] = 1 / M): per-drone models are not built. */
+/* MDS_OK if the configuration runs the FedCE / dLQR entry points below, MDS_EUNSUPPORTED (with mds_last_error naming what is
+ * missing) if not, MDS_EINVAL for NULL.  Touches no device; every entry point below applies it to its handle first. */
+int mds_fedce_supported(const mds_config* cfg);
+/* P0 [256] (row-major 16 x 16) and theta0 [192] (16 x 12, projected on the way in) to every drone. */
+int mds_fedce_init(mds_handle* h, const double P0[256], const double theta0[192]);
+/* Host copies: theta_host [n,16,12] (the projected theta), P_host [n,16,16]; either may be NULL.  Synchronous. */
+int mds_fedce_get(mds_handle* h, double* theta_host, double* P_host);
+int mds_fedce_set(mds_handle* h, const double* theta_host, const double* P_host);
+/* One warm-up (u_mode 0: phi takes the raw u) or exploration phase (u_mode 1: phi takes action_to_input(input_to_action(u)))
+ * of fedCE_iteration, n_steps steps in one launch.  Per step and drone: e_t = error_state(x_t, x_des), phi = [e_t, u~ - (M G, 0,0,0)],
+ * env.step(input_to_action(u)) with the handle's wind, e_{t+1}, x_dot = est_x_dot(e_{t+1}, phi), the pred_errors pair and, with
+ * update != 0, the RLS update + projection.  u_dev [n_steps, n, 4] float64; xdes_dev [n,12] float64 (x_des of the reference,
+ * NULL = zeros; its roll / pitch rates [3:5] are taken as 0, as fedCE sets them); logs (each may be NULL): obs_log_dev [n_steps, n, 20] (storage type), pred_err_log_dev [n_steps, n, 2] and
+ * theta_log_dev [n_steps, n, 12] (float64, the free entries after the step); obs_dev [n,20]: the last observation (or NULL).
+ * Every device buffer is 16-byte aligned (MDS_EALIGN otherwise). */
+int mds_fedce_identify(mds_handle* h, int n_steps, const double* u_dev, int u_mode, const double* xdes_dev, int update, void* obs_log_dev,
+                       double* pred_err_log_dev, double* theta_log_dev, void* obs_dev, void* stream);
+/* The dLQR gain of every env: K_host [E, 4D, 12D] float64 (u = -K e stacked over the env's drones).  Uploaded in the env's
+ * dtype to the device layout [E][4][12D][D] (element (env, q, col, j) = K_env[4j + q][col]).  Synchronous. */
+int mds_set_dlqr_gain(mds_handle* h, const double* K_host);
+/* DecentralizedLQR.compute(obs) for every env: obs_dev [n,20], des_dev [n,11] (pos, vel, -, yaw, omega) -> u_dev [n,4] (the drone's
+ * slice of -K e, before the hover offset) and action_dev [n,4] (input_to_action(u + (M G, 0, 0, 0))); either output may be NULL. */
+int mds_dlqr_compute(mds_handle* h, const void* obs_dev, const void* des_dev, void* u_dev, void* action_dev, void* stream);
+/* n_steps control steps of the dLQR loop (trajectory table -> error state -> coupled -K e -> mixer -> env.step with wind) in one
+ * launch, desired states from mds_set_lemniscate / mds_set_trajectory_segments.  obs_log_dev [n_steps, n, 20] or NULL, obs_last_dev
+ * [n,20] or NULL. */
+int mds_rollout_dlqr_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_last_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

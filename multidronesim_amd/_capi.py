@@ -125,6 +125,14 @@ PROTOTYPES = {
     "mds_rollout_cbf_geometric_fused": (C.c_int, [_P, C.c_double, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mds_step_nominal": (C.c_int, [_P, C.c_double, _P, _P, _P]),
     "mds_rollout_nominal_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
+    "mds_fedce_supported": (C.c_int, [C.POINTER(MdsConfig)]),
+    "mds_fedce_init": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_get": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_set": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_identify": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "mds_set_dlqr_gain": (C.c_int, [_P, _PD]),
+    "mds_dlqr_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "mds_rollout_dlqr_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 #endif
 #if MDS_PART & 2
 #include "mds_cbf_kernels.hip"      // (part 2 only: it defines a non-template kernel)
+#include "mds_fedce_kernels.hip"    // FedCE identification and the dLQR kernels (part 2 only)
 #else
 #include "mds_cbf.hpp"
 #endif
@@ -165,6 +166,10 @@ struct mds_handle {
   bool envfx;          // physics has ground effect and / or downwash
   EnvFx<float> fx_f;
   EnvFx<double> fx_d;
+  // FedCE / dLQR (mds_fedce_*, mds_*dlqr*): per-drone RLS state in float64, per-env gain in the compute type
+  double* fedce_P = nullptr;      // [n][16][16]
+  double* fedce_theta = nullptr;  // [n][12]: the free entries of theta (mds_fedce_kernels.hip)
+  void* dlqr_K = nullptr;         // T [E][4][12 D][D] (dlqr_kidx)
   bool track_rpm;      // last_rpm planes maintained by every step kernel (DYN_DRAG, order-3 CBF, or cfg.track_last_rpm)
   bool rpm_stale;      // a step ran without tracking since the last reset
 };
@@ -536,6 +541,9 @@ int mds_destroy(mds_handle* h) {
   if (h->pid) (void)hipFree(h->pid);
   if (h->segs) (void)hipFree(h->segs);
   if (h->tinfo) (void)hipFree(h->tinfo);
+  if (h->fedce_P) (void)hipFree(h->fedce_P);
+  if (h->fedce_theta) (void)hipFree(h->fedce_theta);
+  if (h->dlqr_K) (void)hipFree(h->dlqr_K);
   if (h->split_st) (void)hipStreamDestroy(h->split_st);
   for (int k = 0; k < 2; ++k)
     if (h->split_ev[k]) (void)hipEventDestroy(h->split_ev[k]);
@@ -2336,6 +2344,208 @@ int mds_step_nominal(mds_handle* h, double t, void* obs, void* action, void* str
   return step_nominal_lowlevel(h, t, obs, nullptr, action, stream, false, "mds_step_nominal");
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// FedCE system identification and the decentralised LQR (mds_fedce_kernels.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+int mds_fedce_supported(const mds_config* cfg) {
+  if (!cfg) return fail(MDS_EINVAL, "mds_fedce_supported: null config");
+  if (cfg->dtype == MDS_F16) return fail(MDS_EUNSUPPORTED, "FedCE / dLQR: fp16 storage is not built (f32 / f64 only)");
+  if (cfg->dtype == MDS_F32C) return fail(MDS_EUNSUPPORTED, "FedCE / dLQR: the compensated MDS_F32C dtype is not built (f32 / f64 only)");
+  if (cfg->integrator != MDS_INTEGRATOR_EULER) return fail(MDS_EUNSUPPORTED, "FedCE / dLQR: RK4 is not built (explicit Euler only)");
+  if (cfg->physics != MDS_PHYSICS_DYN && cfg->physics != MDS_PHYSICS_DYN_DRAG)
+    return fail(MDS_EUNSUPPORTED, "FedCE / dLQR: ground effect / downwash are not built (DYN / DYN_DRAG only)");
+  if (cfg->num_drones < 1 || cfg->num_drones > kFedceMaxD) return fail(MDS_EUNSUPPORTED, "FedCE / dLQR: 1 <= num_drones <= 16 only");
+  return MDS_OK;
+}
+
+static int fedce_ready(mds_handle* h, const char* who) {
+  if (!h) return fail(MDS_EINVAL, who);
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fedce_P) {
+    MDS_HIP(hipMalloc(&h->fedce_P, (size_t)h->n * 256 * sizeof(double)));
+    MDS_HIP(hipMalloc(&h->fedce_theta, (size_t)h->n * 12 * sizeof(double)));
+  }
+  return MDS_OK;
+}
+
+// theta [16,12] (row-major) -> the 12 free entries (project_theta)
+static void fedce_project(const double* th, double f[12]) {
+  f[0] = th[1 * 12 + 6];
+  f[1] = th[0 * 12 + 7];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) f[2 + 3 * a + b] = th[(13 + b) * 12 + 3 + a];
+  f[11] = th[12 * 12 + 8];
+}
+static void fedce_expand(const double f[12], double* th) {
+  for (int k = 0; k < 192; ++k) th[k] = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    th[(3 + k) * 12 + k] = 1.0;          // A[k, 3+k]
+    th[(6 + k) * 12 + 9 + k] = 1.0;      // A[9+k, 6+k]
+  }
+  th[1 * 12 + 6] = f[0];
+  th[0 * 12 + 7] = f[1];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) th[(13 + b) * 12 + 3 + a] = f[2 + 3 * a + b];
+  th[12 * 12 + 8] = f[11];
+}
+
+int mds_fedce_init(mds_handle* h, const double P0[256], const double theta0[192]) {
+  MDS_DEV(h);
+  if (!h || !P0 || !theta0) return fail(MDS_EINVAL, "mds_fedce_init: null argument");
+  if (int rc = fedce_ready(h, "mds_fedce_init")) return rc;
+  double f[12];
+  fedce_project(theta0, f);
+  std::vector<double> P((size_t)h->n * 256), th((size_t)h->n * 12);
+  for (size_t i = 0; i < (size_t)h->n; ++i) {
+    memcpy(&P[i * 256], P0, 256 * sizeof(double));
+    memcpy(&th[i * 12], f, 12 * sizeof(double));
+  }
+  MDS_HIP(hipMemcpy(h->fedce_P, P.data(), P.size() * sizeof(double), hipMemcpyHostToDevice));
+  MDS_HIP(hipMemcpy(h->fedce_theta, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice));
+  return MDS_OK;
+}
+
+int mds_fedce_get(mds_handle* h, double* theta_host, double* P_host) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_fedce_get: null handle");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fedce_P) return fail(MDS_ESTATE, "mds_fedce_get: call mds_fedce_init first");
+  MDS_HIP(hipDeviceSynchronize());
+  if (P_host) MDS_HIP(hipMemcpy(P_host, h->fedce_P, (size_t)h->n * 256 * sizeof(double), hipMemcpyDeviceToHost));
+  if (theta_host) {
+    std::vector<double> f((size_t)h->n * 12);
+    MDS_HIP(hipMemcpy(f.data(), h->fedce_theta, f.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)h->n; ++i) fedce_expand(&f[i * 12], theta_host + i * 192);
+  }
+  return MDS_OK;
+}
+
+int mds_fedce_set(mds_handle* h, const double* theta_host, const double* P_host) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_fedce_set: null handle");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fedce_P) return fail(MDS_ESTATE, "mds_fedce_set: call mds_fedce_init first");
+  MDS_HIP(hipDeviceSynchronize());
+  if (P_host) MDS_HIP(hipMemcpy(h->fedce_P, P_host, (size_t)h->n * 256 * sizeof(double), hipMemcpyHostToDevice));
+  if (theta_host) {
+    std::vector<double> f((size_t)h->n * 12);
+    for (size_t i = 0; i < (size_t)h->n; ++i) fedce_project(theta_host + i * 192, &f[i * 12]);
+    MDS_HIP(hipMemcpy(h->fedce_theta, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return MDS_OK;
+}
+
+int mds_fedce_identify(mds_handle* h, int n_steps, const double* u_dev, int u_mode, const double* xdes_dev, int update, void* obs_log_dev,
+                       double* pred_err_log_dev, double* theta_log_dev, void* obs_dev, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_fedce_identify: null handle");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (n_steps < 0 || (n_steps > 0 && !u_dev) || (u_mode != 0 && u_mode != 1)) return fail(MDS_EINVAL, "mds_fedce_identify: n_steps / u_dev / u_mode");
+  if (!h->fedce_P) return fail(MDS_ESTATE, "mds_fedce_identify: call mds_fedce_init first");
+  if (!aligned16(obs_log_dev) || !aligned16(obs_dev) || !aligned16(theta_log_dev) || !aligned16(pred_err_log_dev) || !aligned16(u_dev) ||
+      !aligned16(xdes_dev))
+    return fail(MDS_EALIGN, "mds_fedce_identify: u / xdes / log / obs buffers");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_steps > 0) {
+    const FedceModel fm = {h->cfg.M * h->cfg.G, h->cfg.G, h->cfg.M, {h->cfg.J[0], h->cfg.J[1], h->cfg.J[2]}, 1.0 / h->cfg.ctrl_freq};
+    const dim3 grid = grid_for(h->n * 16, kFedceBlock);
+    const bool drag = has_drag(h);
+#define MDS_FEDCE_ID(T, C, DRAG)                                                                                                    \
+    k_fedce_identify<T, T, DRAG><<<grid, kFedceBlock, 0, st>>>(C, h->cd, fm, h->n, h->ld, n_steps, (T*)h->state, (const T*)h->origin,     \
+                                                               (T*)rpm_track(h), u_dev, u_mode, xdes_dev, update, h->fedce_P,          \
+                                                               h->fedce_theta, (T*)obs_log_dev, pred_err_log_dev, theta_log_dev)
+    if (h->cfg.dtype == MDS_F64) {
+      if (drag) MDS_FEDCE_ID(double, h->cd, true);
+      else MDS_FEDCE_ID(double, h->cd, false);
+    } else {
+      if (drag) MDS_FEDCE_ID(float, h->cf, true);
+      else MDS_FEDCE_ID(float, h->cf, false);
+    }
+#undef MDS_FEDCE_ID
+    MDS_HIP(hipGetLastError());
+  }
+  if (obs_dev) {
+    if (obs_log_dev && n_steps > 0) {
+      const size_t obs_bytes = (size_t)h->n * kObsDim * elem_size(h->cfg.dtype);
+      MDS_HIP(hipMemcpyAsync(obs_dev, (char*)obs_log_dev + (size_t)(n_steps - 1) * obs_bytes, obs_bytes, hipMemcpyDeviceToDevice, st));
+    } else {
+      return mds_get_obs(h, obs_dev, stream);
+    }
+  }
+  return MDS_OK;
+}
+
+int mds_set_dlqr_gain(mds_handle* h, const double* K_host) {
+  MDS_DEV(h);
+  if (!h || !K_host) return fail(MDS_EINVAL, "mds_set_dlqr_gain: null argument");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones;
+  const size_t per = (size_t)48 * D * D, total = per * E;
+  const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
+  if (!h->dlqr_K) MDS_HIP(hipMalloc(&h->dlqr_K, total * es));
+  std::vector<double> kd(h->cfg.dtype == MDS_F64 ? total : 0);
+  std::vector<float> kf(h->cfg.dtype == MDS_F64 ? 0 : total);
+  for (size_t e = 0; e < (size_t)E; ++e)
+    for (int j = 0; j < D; ++j)
+      for (int q = 0; q < 4; ++q)
+        for (int col = 0; col < 12 * D; ++col) {
+          const double v = K_host[e * per + (size_t)(4 * j + q) * (12 * D) + col];
+          const size_t at = dlqr_kidx(e, D, j, q, col);
+          if (kd.size()) kd[at] = v;
+          else kf[at] = (float)v;
+        }
+  MDS_HIP(hipDeviceSynchronize());
+  MDS_HIP(hipMemcpy(h->dlqr_K, kd.size() ? (const void*)kd.data() : (const void*)kf.data(), total * es, hipMemcpyHostToDevice));
+  return MDS_OK;
+}
+
+int mds_dlqr_compute(mds_handle* h, const void* obs, const void* des, void* u, void* action, void* stream) {
+  MDS_DEV(h);
+  if (!h || !obs || !des || (!u && !action)) return fail(MDS_EINVAL, "mds_dlqr_compute: null argument");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->dlqr_K) return fail(MDS_ESTATE, "mds_dlqr_compute: call mds_set_dlqr_gain first");
+  if (!aligned16(u) || !aligned16(action)) return fail(MDS_EALIGN, "mds_dlqr_compute: u_dev/action_dev");
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones, epb = kFedceBlock / D;
+  const dim3 grid((unsigned)((E + epb - 1) / epb));
+  if (h->cfg.dtype == MDS_F64)
+    k_dlqr_compute<double, double><<<grid, kFedceBlock, 0, (hipStream_t)stream>>>(h->cd, (const double*)h->dlqr_K, E, D, (const double*)obs,
+                                                                                  (const double*)des, (double*)u, (double*)action);
+  else
+    k_dlqr_compute<float, float><<<grid, kFedceBlock, 0, (hipStream_t)stream>>>(h->cf, (const float*)h->dlqr_K, E, D, (const float*)obs,
+                                                                                (const float*)des, (float*)u, (float*)action);
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+
+int mds_rollout_dlqr_fused(mds_handle* h, double t0, int n_steps, void* obs_log, void* obs_last, void* stream) {
+  MDS_DEV(h);
+  if (!h || n_steps < 0) return fail(MDS_EINVAL, "mds_rollout_dlqr_fused: null handle / n_steps");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->has_traj) return fail(MDS_ESTATE, "mds_rollout_dlqr_fused: call mds_set_lemniscate / mds_set_trajectory_segments first");
+  if (!h->dlqr_K) return fail(MDS_ESTATE, "mds_rollout_dlqr_fused: call mds_set_dlqr_gain first");
+  if (!aligned16(obs_log) || !aligned16(obs_last)) return fail(MDS_EALIGN, "mds_rollout_dlqr_fused: obs buffers");
+  if (n_steps == 0) return MDS_OK;
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones, epb = kFedceBlock / D;
+  const dim3 grid((unsigned)((E + epb - 1) / epb));
+  const double dt = 1.0 / h->cfg.ctrl_freq;
+  hipStream_t st = (hipStream_t)stream;
+#define MDS_DLQR(T, C, DRAG)                                                                                                         \
+  k_dlqr_rollout<T, T, DRAG><<<grid, kFedceBlock, 0, st>>>(C, (const T*)h->dlqr_K, E, D, h->ld, t0, dt, n_steps, h->traj_mode, (T*)h->state, \
+                                                           (const T*)h->origin, (const T*)h->lem, SegTable{h->segs, h->nseg_total},       \
+                                                           h->tinfo, (T*)rpm_track(h), (T*)obs_log, (T*)obs_last)
+  const bool drag = has_drag(h);
+  if (h->cfg.dtype == MDS_F64) {
+    if (drag) MDS_DLQR(double, h->cd, true);
+    else MDS_DLQR(double, h->cd, false);
+  } else {
+    if (drag) MDS_DLQR(float, h->cf, true);
+    else MDS_DLQR(float, h->cf, false);
+  }
+#undef MDS_DLQR
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
 #endif  // MDS_PART & 2
 
 }  // extern "C"

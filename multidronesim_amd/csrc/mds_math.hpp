@@ -761,10 +761,10 @@ MDS_HD void lqr_omega_control(const Consts<T>& c, const LqrGain<T>& K, V3<T> rpy
 template <typename T> struct Lqr12Gain {
   T k[4][12];
 };
+// The 12-state error of lqr_controller.py (and DecentralizedLQR.error_state, control/dlqr/decentralized_lqr.py:288-298):
+// (roll, pitch, wrapped yaw error, then the R_eq^T-rotated w, v and p errors; only yaw_des enters R_eq).
 template <typename T>
-MDS_HD void lqr12_control(const Consts<T>& c, const Lqr12Gain<T>& K, V3<T> rpy, V3<T> angv_world, V3<T> vel, V3<T> pos_err, V3<T> vel_des,
-                          T yaw_des, T omega_des, T u[4]) {
-  T e[12];
+MDS_HD void lqr12_error(V3<T> rpy, V3<T> angv_world, V3<T> vel, V3<T> pos_err, V3<T> vel_des, T yaw_des, T omega_des, T e[12]) {
   e[0] = rpy.x;
   e[1] = rpy.y;
   const T dy = rpy.z - yaw_des;
@@ -775,6 +775,12 @@ MDS_HD void lqr12_control(const Consts<T>& c, const Lqr12Gain<T>& K, V3<T> rpy, 
   e[3] = cy * dw.x + sy * dw.y; e[4] = -sy * dw.x + cy * dw.y; e[5] = dw.z;
   e[6] = cy * dv.x + sy * dv.y; e[7] = -sy * dv.x + cy * dv.y; e[8] = dv.z;
   e[9] = cy * dp.x + sy * dp.y; e[10] = -sy * dp.x + cy * dp.y; e[11] = dp.z;
+}
+template <typename T>
+MDS_HD void lqr12_control(const Consts<T>& c, const Lqr12Gain<T>& K, V3<T> rpy, V3<T> angv_world, V3<T> vel, V3<T> pos_err, V3<T> vel_des,
+                          T yaw_des, T omega_des, T u[4]) {
+  T e[12];
+  lqr12_error<T>(rpy, angv_world, vel, pos_err, vel_des, yaw_des, omega_des, e);
   for (int r = 0; r < 4; ++r) {
     T acc = T(0);
     for (int k = 0; k < 12; ++k) acc = m_fma(-K.k[r][k], e[k], acc);

@@ -7,8 +7,13 @@ observations.append(obs) -- run as fused kernels for every drone of every env.  
 (default 1 = the reference).  ``self.observations`` ends up as the reference leaves it: one [D,20] array per
 control step (``np.save(path, geo.observations)`` -> [T,D,20], :553; with num_envs > 1: [T,E,D,20]).
 
-Controllers: 'lqr' (LQRController on the 12-state LinearizedModel, the script's default, incl. ``use_noisy_model``) and
-'geometric'.  Out of scope here: 'dlqr' and ``fedCE*`` (system identification)."""
+Controllers: 'lqr' (LQRController on the 12-state LinearizedModel, the script's default, incl. ``use_noisy_model``),
+'geometric' and 'dlqr' (DecentralizedLQR with ``computed_K=`` or the gain of the last ``fedCE()`` on this GeometricEnv).
+
+``fedCE(num_iter, record_results)`` / ``fedCE_iteration`` (:113-325): the default loop (random warm-up, set-point or Lemniscate
+CE phase) with every phase one kernel launch -- identification (mds_fedce_identify) and dLQR control (mds_rollout_dlqr_fused);
+the Riccati solve runs on the host once per iteration.  Noise: the reference's global np.random draws with one env, a torch.Generator
+on the device (``generator=``) with several; ``noise=`` injects draws.  Not built: ``random_warmup=False``, ``warm_up_only``."""
 from __future__ import annotations
 
 import argparse
@@ -32,7 +37,7 @@ DEFAULT_CONTROL_FREQ_HZ = 100
 DEFAULT_DURATION_SEC = 30
 DEFAULT_OUTPUT_FOLDER = 'results'
 DEFAULT_NUM_DRONES = 2
-controllers = ['lqr', 'geometric']       # whichever is first is the default (:32); 'dlqr' (FedCE) is not on this path
+controllers = ['lqr', 'geometric', 'dlqr']       # whichever is first is the default (:32, where 'dlqr' is selected with --controller)
 wind_force = .00025
 
 
@@ -72,6 +77,10 @@ class GeometricEnv:
         self.wind_force = wind_force
         self._use_noisy_model = False
         self._step = None
+        self._fedce_K = None              # the gain of the last fedCE() ('dlqr' in do_control)
+        self._computed_K = None           # do_control(computed_K=...)
+        self.fedce_thetas, self.fedce_Ks = [], []   # fedCE(log_iterations=True): theta and K after every iteration
+        self.fedce_observations = []      # fedCE(log_observations=True): every observation env.step returned, in order
         if circle_init:
             self.starting_target_offset = 1
             self.circle_initialize()
@@ -104,8 +113,15 @@ class GeometricEnv:
             self._step = env.step_lqr
         elif args.controller == 'geometric':
             self._step = env.step_geometric
+        elif args.controller == 'dlqr' and (self._computed_K is not None or self._fedce_K is not None):
+            from ..control import DecentralizedLQR
+            dlqr = DecentralizedLQR(env, self.linear_models)                          # :416-419, with the gain the reference leaves undefined
+            dlqr.upload_gain(self._computed_K if self._computed_K is not None else self._fedce_K)
+            self._dlqr = dlqr
+            self._step = lambda t: (dlqr.rollout(t, 1, log=False), env._obs)[1]
         else:
-            raise NotImplementedError(f"controller {args.controller!r}: the dLQR / FedCE parts of this script are outside the hot path")
+            raise NotImplementedError(f"controller {args.controller!r}: 'dlqr' needs a gain -- do_control(computed_K=...) or a fedCE() "
+                                      "on this GeometricEnv first")
         if trajs is None:                 # set-point regulation towards TARGET_POSITIONS / TARGET_RPYS[:, 2] (:449-455)
             trajs = [WaitTrajectory(duration=float(args.duration_sec), position=self.TARGET_POSITIONS[j], yaw=self.TARGET_RPYS[j, 2])  # noqa: F405
                      for j in range(args.num_drones)]
@@ -120,9 +136,10 @@ class GeometricEnv:
         self.observations.append(self.obs)
         self.obs_ts.append(t)
 
-    def do_control(self, trajs=None, render=False, use_noisy_model=False, wind=True):
+    def do_control(self, trajs=None, render=False, use_noisy_model=False, wind=True, computed_K=None):
         env = self.env
         self._use_noisy_model = use_noisy_model
+        self._computed_K = computed_K
         steps = self._start(trajs)
         if wind:
             env.set_wind([self.wind_force, 0.0, 0.0])                                  # :463-467, every step, every drone
@@ -137,8 +154,11 @@ class GeometricEnv:
                 env.render()
                 sync(i, START, env.CTRL_TIMESTEP)
         else:                             # the same loop on the device, observations logged there
-            log = torch.empty((steps, env.NUM_ENVS, env.NUM_DRONES, 20), dtype=env.dtype, device=env.device)
-            env.rollout_geometric_fused(0.0, steps, log=True, log_out=log, controller=args_controller)   # one launch: state in registers
+            if self.args.controller == 'dlqr':
+                log = self._dlqr.rollout(0.0, steps, log=True)
+            else:
+                log = torch.empty((steps, env.NUM_ENVS, env.NUM_DRONES, 20), dtype=env.dtype, device=env.device)
+                env.rollout_geometric_fused(0.0, steps, log=True, log_out=log, controller=args_controller)   # one launch: state in registers
             for i in range(steps):
                 self.obs_ts.append(t)
                 t += env.CTRL_TIMESTEP
@@ -146,6 +166,110 @@ class GeometricEnv:
             self.observations.extend(list(o[:, 0] if env.NUM_ENVS == 1 else o))
             self.obs = self.observations[-1]
         env.close()
+
+    # ------------------------------------------------------------------ FedCE (:113-325)
+    def fedCE(self, num_iter=15, record_results=False, noise=None, generator=None, do_lemniscate=False, log_observations=False,
+              log_iterations=False):
+        """-> (K, theta) of the last iteration, as the reference.  ``noise``: per iteration (u_warm [25,(E,)D,4] or None,
+        u_explore [Texp,(E,)D,4]) raw draws instead of sigma1 / sigma_explore.  ``log_iterations`` keeps theta and K of every
+        iteration in fedce_thetas / fedce_Ks.  Closes the env like the reference (:151)."""
+        from ..control import DecentralizedLQR
+        env, D = self.env, self.args.num_drones
+        dLQR = DecentralizedLQR(env, self.linear_models)
+        START = time.time()
+        steps = 0
+        preds = []
+        self.fedce_observations = []
+        self.fedce_thetas, self.fedce_Ks = [], []
+        for n in range(num_iter):
+            steps = self.fedCE_iteration(env, dLQR, START, steps, n, do_warmup=(n == 0), random_warmup=True, do_lemniscate=do_lemniscate,
+                                         noise=None if noise is None else noise[n], generator=generator, log_observations=log_observations)
+            if log_iterations:
+                self.fedce_thetas.append(dLQR.theta)
+                self.fedce_Ks.append(np.copy(dLQR.K))
+            if record_results:
+                theta = dLQR._stack(dLQR._get()[0])                                   # [E, 16D, 12D]
+                A = theta[:, :12 * D, :].swapaxes(1, 2)
+                B = theta[:, 12 * D:, :].swapaxes(1, 2)
+                rows = []
+                for i in range(D):
+                    Ai = A[:, i * 12:(i + 1) * 12, i * 12:(i + 1) * 12]
+                    Bi = B[:, i * 12:(i + 1) * 12, i * 4:(i + 1) * 4]
+                    rows.append(np.concatenate([Ai[:, 6, 1:2], Ai[:, 7, 0:1], Ai[:, :3, 3:6].reshape(-1, 9), Ai[:, 9:, 6:9].reshape(-1, 9),
+                                                Bi[:, 3:6, 1:].reshape(-1, 9), Bi[:, 8, 0:1]], axis=1))
+                preds.append(np.stack(rows, axis=1))                                   # [E, D, 30]
+                print(f"n: {n}, steps: {steps}")
+        if record_results:
+            E = env.NUM_ENVS
+            pe = np.array(dLQR.pred_errors, dtype=np.float64)                          # [2D, U] or [2D, U, E]
+            pt = np.array(dLQR.pred_thetas, dtype=np.float64)                          # [D, U, 12, 16] or [D, U, E, 12, 16]
+            if E == 1:
+                np.save("predictions.npy", np.array(preds)[:, 0])
+            else:
+                np.save("predictions.npy", np.array(preds).transpose(1, 0, 2, 3))
+                pe = np.moveaxis(pe, -1, 0) if pe.ndim == 3 else np.zeros((E,) + pe.shape)
+                pt = np.moveaxis(pt, 2, 0) if pt.ndim == 5 else np.zeros((E,) + pt.shape)
+            np.save("pred_errors.npy", pe)
+            np.save("pred_thetas.npy", pt)
+        theta = dLQR.theta
+        self._fedce_K = dLQR.K
+        self.dLQR = dLQR
+        env.close()
+        return dLQR.K, theta
+
+    def fedCE_iteration(self, env, dLQR, START, steps, n, k=2, do_warmup=True, random_warmup=True, do_lemniscate=False, do_print=False,
+                        noise=None, generator=None, log_observations=False):
+        """One FedCE iteration (:154-325): [25-step random warm-up], compute_controller, 4n CE steps, min(2n, 40) exploration steps,
+        each phase one launch.  The reference's loop-variable quirk is kept: its `if i != 0` tests the wind loop's D - 1, so every
+        step updates when D >= 2 and none when D == 1."""
+        from ..control.dlqr.decentralized_lqr import U_RAW, U_ROUND_TRIP
+        from ..trajectories import Lemniscate, WaitTrajectory
+        if not random_warmup:
+            raise NotImplementedError("fedCE_iteration(random_warmup=False): the LQR-driven warm-up is not built")
+        args, D, E = self.args, self.args.num_drones, env.NUM_ENVS
+        Texp = min(n * k, 20 * k)
+        Tce = k * n * 2
+        Tw = 25 if do_warmup else 0
+        update = (D - 1) != 0
+        env.set_wind([0.0, 0.0, 0.0])
+        obs, _, _, _, _ = env.step(torch.zeros((E, D, 4), dtype=env.dtype, device=env.device))   # :169-170
+        logs = [obs.clone()[None]] if log_observations else None
+        env.set_wind([self.wind_force, 0.0, 0.0])                                    # :206-210, :264-267, :301-305
+        if Tw:
+            x_des = np.zeros((D, 12))
+            x_des[:, 0:3] = self.INIT_RPYS
+            x_des[:, 9:12] = self.INIT_XYZS
+            u = noise[0] if noise is not None else dLQR.draw_inputs("warmup", Tw, generator)
+            log, obs = dLQR.identify(u, U_RAW, x_des, update, log_obs=log_observations)
+            if log_observations:
+                logs.append(log)
+            steps += Tw
+        last_desired = np.zeros((D, 12))
+        dLQR.compute_controller()
+        if Tce:
+            if do_lemniscate:
+                traj = Lemniscate(center=np.array([0, 0, .5]), omega=1, yaw_rate=.1)
+                env.set_trajectories([traj] * D)
+            else:
+                env.set_trajectories([WaitTrajectory(position=self.TARGET_POSITIONS[j], duration=Tce * env.CTRL_TIMESTEP + 1.0,
+                                                     yaw=self.TARGET_RPYS[j, 2]) for j in range(D)])
+                last_desired = np.hstack([self.TARGET_RPYS, np.zeros((D, 6)), self.TARGET_POSITIONS])
+            log = dLQR.rollout(0.0, Tce, log=log_observations)
+            if log_observations:
+                logs.append(log)
+            steps += Tce
+        if Texp:
+            u = noise[1] if noise is not None else dLQR.draw_inputs("explore", Texp, generator)
+            log, obs = dLQR.identify(u, U_ROUND_TRIP, last_desired, update, log_obs=log_observations)
+            if log_observations:
+                logs.append(log)
+            steps += Texp
+        if log_observations:
+            o = torch.cat([l.reshape(-1, E, D, 20) for l in logs]).double().cpu().numpy()
+            self.fedce_observations.extend(list(o[:, 0] if E == 1 else o))
+        self.obs = env._obs.double().cpu().numpy()
+        self.obs = self.obs[0] if E == 1 else self.obs
+        return steps
 
     def geometric_xdot(self, obs):
         """[v_world, w_body, R^T [0,0,F/m], 0] from one observation (:483-500)."""
