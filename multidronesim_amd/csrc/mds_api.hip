@@ -125,10 +125,6 @@ struct mds_handle {
   // stream, ev[1] joins it back.  Created (and primed) by mds_create for shards that can split, else by mds_set_rollout_streams(h, 2).
   hipStream_t split_st = nullptr;
   hipEvent_t split_ev[2] = {nullptr, nullptr};
-  int split_lds = 32768;                // LDS bytes a half-shard workgroup occupies in a two-chain rollout (MDS_TUNE_SPLIT_LDS, tuning only)
-  int split_offset = 0;                 // 1: the fork event sits half way through chain 0's first step (MDS_TUNE_SPLIT_OFFSET, tuning only; the
-                                        // fork's own latency already starts chain 1 about half a kernel late: 20-step calls 17.3 vs 17.6 us)
-  int split_min_steps = 0;              // auto policy: calls shorter than this stay on one stream (MDS_TUNE_SPLIT_MIN_STEPS, tuning only)
   int last_rollout_streams = 0;         // what the last mds_rollout_* call did (mds_get_last_rollout_streams)
   int rollout_form = 0;                 // mds_set_rollout_form: 0 auto, 1 one launch per control step, 2 the whole-rollout kernel in chunks
   int rollout_chunk = 50;               // control steps per launch of form 2
@@ -138,7 +134,6 @@ struct mds_handle {
   bool cbf_hildreth = false;            // MDS_CBF_SOLVER=hildreth, read once by mds_cbf_configure
   bool cbf_q4 = false;                  // MDS_CBF_Q4=1 at configure time: the four-envs-per-wave QP kernel (k_cbf_filter_q4) where it applies; measured
                                         // no faster than one env per wave (see its header), so opt-in
-  bool cbf_chain_nominal = true;        // MDS_CBF_CHAIN=0 at configure time: the C rollout loops launch the nominal kernel every step (A/B)
   int cbf_last_step_kernel = -1;        // what the most recent CBF-filtered step launched: 1 the one-launch kernel, 0 QP + low level
   bool cbf_step_persistent = false;     // mds_cbf_set_step_kernel(h, 2): a CBF-filtered step = one launch of the persistent rollout kernel where it applies
   bool cbf_fused = false;               // mds_cbf_set_step_kernel / MDS_CBF_FUSED=1 at configure time: the one-launch CBF step (k_cbf_step) where it applies; it wins only
@@ -193,10 +188,10 @@ constexpr size_t kSplitMinDrones = size_t(1) << 18;
 // per control step (enqueue .. synchronize, median of 21 calls) by call length, one stream -> two chains: 8 steps 20.3 -> 20.8,
 // 12 steps 19.0 -> 19.0, 16 steps 19.0 -> 18.1, 20 steps 18.7 -> 17.7, 32 steps 18.2 -> 16.9, 48 steps 18.0 -> 16.5; by HIP events
 // 100 steps 17.4 -> 15.2, 2000 steps 17.4 -> 14.8 (profiles/r02_short_calls.log).
-#ifndef MDS_SPLIT_MIN_STEPS
-#define MDS_SPLIT_MIN_STEPS 16
-#endif
-constexpr int kSplitMinSteps = MDS_SPLIT_MIN_STEPS;
+constexpr int kSplitMinSteps = 16;
+// LDS bytes a half-shard workgroup occupies in a two-chain rollout: its launch carries unused dynamic LDS up to this
+// (launch_step_geometric says why)
+constexpr size_t kSplitLds = 32768;
 
 // The stream policy in one place (mds_set_rollout_streams; mds_rollout_streams_for reports it).  loop 0: the fused geometric /
 // plain env.step loops (size sweep of DESIGN.md 4: below 2^18 drones the extra launches cost more than the overlap gains,
@@ -206,9 +201,8 @@ static int rollout_streams_policy(const mds_handle* h, int loop, int n_steps) {
   if (n_steps < 2 || !h->split_st || h->envfx) return 1;     // ground effect / downwash: the substeps swap two state buffers, one chain
   if (h->rollout_streams) return h->rollout_streams;
   const size_t n = (size_t)h->n;
-  const int min_steps = h->split_min_steps > 0 ? h->split_min_steps : kSplitMinSteps;
-  if (loop == 1) return (n >= kSplitMinDrones / 4 && n_steps >= min_steps) ? 2 : 1;
-  const bool big = n >= 2 * kSplitMinDrones ? n_steps >= min_steps : (n >= kSplitMinDrones && n_steps >= 1000);
+  if (loop == 1) return (n >= kSplitMinDrones / 4 && n_steps >= kSplitMinSteps) ? 2 : 1;
+  const bool big = n >= 2 * kSplitMinDrones ? n_steps >= kSplitMinSteps : (n >= kSplitMinDrones && n_steps >= 1000);
   return big ? 2 : 1;
 }
 
@@ -220,20 +214,15 @@ static int rollout_streams_policy(const mds_handle* h, int loop, int n_steps) {
 // per step against 1.9; one eighth of config 3, 65 536 drones, 4.75 against 1.97), above it form 1 streams the 13-value state through HBM
 // twice per step (212 B per drone-step at 0.8-0.93 of the roofline: config 3 15.4 us per step) where form 2 moves the observation row only
 // (82.6 B: 7.5-9.0 us, VALU-bound).  float64 likewise (config 3: 32.7 -> 30.9 us per step, 4 M drones 330 -> 246; its whole-rollout kernel is
-// arithmetic-bound -- software sin / cos / atan2 / asin, divisions -- and wins by less).  MDS_FUSED_MAX_DRONES (compile time) caps the window for A/B
-// builds.  fp16 storage stays in form 1 (form 2 rounds the state to fp16 once per launch instead of once per step: not the same arithmetic).
-#ifndef MDS_FUSED_MAX_DRONES
-#define MDS_FUSED_MAX_DRONES (~size_t(0))
-#endif
-constexpr size_t kFusedMinDrones = size_t(1) << 13, kFusedMaxDrones = MDS_FUSED_MAX_DRONES;
+// arithmetic-bound -- software sin / cos / atan2 / asin, divisions -- and wins by less).  fp16 storage stays in form 1 (form 2 rounds the
+// state to fp16 once per launch instead of once per step: not the same arithmetic).
+constexpr size_t kFusedMinDrones = size_t(1) << 13;
 constexpr int kFusedMinSteps = 8;
 static int rollout_form_policy(const mds_handle* h, int n_steps) {
   if (h->envfx || n_steps < 1) return 1;          // ground effect / downwash: env-mates interact every substep, no state-in-registers form
   if (h->rollout_form) return h->rollout_form;
   if (h->cfg.dtype == MDS_F16) return 1;
-  const size_t n = (size_t)h->n;
-  const size_t nmax = kFusedMaxDrones;
-  return (n >= kFusedMinDrones && n <= nmax && n_steps >= kFusedMinSteps) ? 2 : 1;
+  return ((size_t)h->n >= kFusedMinDrones && n_steps >= kFusedMinSteps) ? 2 : 1;
 }
 
 // Set-up path (mds_create / mds_set_rollout_streams): the internal stream and the two events of the two-chain rollouts.
@@ -312,14 +301,7 @@ static void launch_compare_models(const Consts<T>& C, int count, const void* obs
                                   const double* dyn_J, double dyn_g, void* xdot_lin, void* xdot_geo, void* x_lin, hipStream_t st) {
   LinModel<T> M;
   fill_lin_model<T>(A, B, u_eq0, M);
-  // MDS_TUNE_CMP_LDS: unused dynamic LDS per workgroup (tuning only: fewer resident workgroups per CU, so that the launch runs in rounds
-  // whose load and store phases overlap instead of one round in lock step); out-of-range values are ignored
-  static const size_t pad = [] {
-    const char* v = getenv("MDS_TUNE_CMP_LDS");
-    const long x = v ? atol(v) : 0;
-    return (size_t)((x > 0 && x <= 120 * 1024) ? x : 0);
-  }();
-  k_compare_models<T, S><<<grid_for(count, kBlock), kBlock, pad, st>>>(C, M, count, (const S*)obs, (T)dyn_m, (T)dyn_J[0], (T)dyn_J[1], (T)dyn_J[2],
+  k_compare_models<T, S><<<grid_for(count, kBlock), kBlock, 0, st>>>(C, M, count, (const S*)obs, (T)dyn_m, (T)dyn_J[0], (T)dyn_J[1], (T)dyn_J[2],
                                                                       (T)dyn_g, (S*)xdot_lin, (S*)xdot_geo, (S*)x_lin);
 }
 template <typename T, typename S>
@@ -492,19 +474,6 @@ int mds_create(const mds_config* cfg, mds_handle** out) {
   }
   // shards large enough for the auto policy of the two-chain rollouts get their streams and events now (smallest auto
   // threshold: the CBF loop, 2^16 drones); smaller ones only if mds_set_rollout_streams(h, 2) asks for them
-  // tuning variables: garbage or out-of-range values fall back to the defaults instead of turning into an opaque launch failure
-  // (a negative LDS pad cast to size_t, or one above what a workgroup may own, fails every two-chain launch)
-  if (const char* v = getenv("MDS_TUNE_SPLIT_OFFSET")) h->split_offset = atoi(v) == 1 ? 1 : 0;
-  if (const char* v = getenv("MDS_TUNE_SPLIT_LDS")) {
-    const long lds = strtol(v, nullptr, 10);
-    int lds_max = 0;
-    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device) != hipSuccess) lds_max = 65536;
-    h->split_lds = (lds >= 0 && lds <= lds_max - (long)(kBlock * kObsDim * 8)) ? (int)lds : 32768;
-  }
-  if (const char* v = getenv("MDS_TUNE_SPLIT_MIN_STEPS")) {
-    const long ms = strtol(v, nullptr, 10);
-    h->split_min_steps = (ms >= 0 && ms <= 1000000) ? (int)ms : 0;
-  }
   if ((size_t)h->n >= kSplitMinDrones / 4) {
     if (int rc = split_streams_ready(h)) {
       mds_destroy(h);
@@ -671,7 +640,7 @@ static void launch_step_plain(mds_handle* h, const void* action, void* obs, hipS
   size_t pad = 0;
   if (nb) {
     const size_t static_lds = obs ? (size_t)kBlock * kObsDim * elem_size(h->cfg.dtype) : 16;
-    pad = static_lds < (size_t)h->split_lds ? (size_t)h->split_lds - static_lds : 0;
+    pad = static_lds < kSplitLds ? kSplitLds - static_lds : 0;
   }
 #define MDS_LAUNCH_STEP(HAS_OBS, RK4, DRAG)                                                                          \
   do {                                                                                                               \
@@ -962,7 +931,7 @@ static int launch_step_geometric(mds_handle* h, double t, void* obs, void* act, 
   size_t pad = 0;
   if (nb) {
     const size_t static_lds = (h->traj_mode == 2 || obs) ? (size_t)kBlock * kObsDim * elem_size(h->cfg.dtype) : 16;
-    pad = static_lds < (size_t)h->split_lds ? (size_t)h->split_lds - static_lds : 0;
+    pad = static_lds < kSplitLds ? kSplitLds - static_lds : 0;
   }
   if (h->traj_mode == 2) {      // general trajectories: segment tables
     const bool rk4_ = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag_ = has_drag(h);
@@ -1112,17 +1081,9 @@ int mds_rollout_geometric(mds_handle* h, double t0, int n_steps, void* obs, int 
     auto body = [&]() -> int {
       for (int k = 0; k < n_steps; ++k) {
         void* o = (obs_every_step || k == n_steps - 1) ? obs : nullptr;
-        if (k == 0 && h->split_offset && half >= 2) {
-          // phase offset: the fork event sits half way through chain 0's first step, so chain 1 starts half a kernel late
-          // (started together the chains begin in lock step and need a few hundred steps to drift apart)
-          launch_step_geometric(h, t0, o, nullptr, st, 0, half / 2);
+        if (k == 0)
           if (int rc = split_fork(h, st)) return rc;
-          launch_step_geometric(h, t0, o, nullptr, st, half / 2, half - half / 2);
-        } else {
-          if (k == 0)
-            if (int rc = split_fork(h, st)) return rc;
-          launch_step_geometric(h, t0, o, nullptr, st, 0, half);
-        }
+        launch_step_geometric(h, t0, o, nullptr, st, 0, half);
         launch_step_geometric(h, t0, o, nullptr, sb, half, nbatch - half);
         t0 += dt;
       }
@@ -1496,8 +1457,6 @@ int mds_cbf_configure(mds_handle* h, const mds_cbf_params* p, const double* obst
     h->cbf_hildreth = solver && solver[0] == 'h';
     const char* q4e = getenv("MDS_CBF_Q4");
     h->cbf_q4 = q4e && q4e[0] == '1';
-    const char* chain = getenv("MDS_CBF_CHAIN");
-    h->cbf_chain_nominal = !(chain && chain[0] == '0');
     if (const char* fused = getenv("MDS_CBF_FUSED")) h->cbf_fused = fused[0] == '1';       // unset: what mds_cbf_set_step_kernel chose
   }
   h->cbf = *p;
@@ -2105,8 +2064,8 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
 // what k_cbf_rollout covers (mds_rollout_cbf_geometric_fused; mds_cbf_set_step_kernel(h, 2))
 static bool roll_fused_applies(const mds_handle* h) {
   const int D = h->cfg.num_drones;
-  const int m2 = D * (D - 1) / 2 + (MDS_ROLL_BOUNDS ? 0 : D * h->cbf.n_obs) + 2 * D;      // (MDS_ROLL_BOUNDS: obstacle rows are per-drone bounds)
-  return h->has_cbf && h->cbf.order == 2 && !h->cbf_hildreth && D >= 1 && D <= 16 && (MDS_ROLL_BOUNDS || 64 % D == 0) && m2 <= 256 && !h->envfx &&
+  const int m2 = D * (D - 1) / 2 + 2 * D;                      // pair rows and two bound rows per drone (obstacles are per-drone bounds)
+  return h->has_cbf && h->cbf.order == 2 && !h->cbf_hildreth && D >= 1 && D <= 16 && m2 <= 256 && !h->envfx &&
          h->cfg.integrator == MDS_INTEGRATOR_EULER && !has_drag(h) && h->cbf_nominal <= 1 && h->cfg.dtype != MDS_F16 &&
          h->cfg.pyb_freq == h->cfg.ctrl_freq && h->n <= (1 << 27);
 }
@@ -2161,7 +2120,7 @@ int mds_rollout_cbf_geometric(mds_handle* h, double t0, int n_steps, void* obs, 
         // from its second step on a chain is two launches per step: QP, low level
         for (int s = 0; s < 2; ++s)
           if (int rc = step_nominal_lowlevel(h, t, obs, status, nullptr, s == 0 ? st : h->split_st, true, "mds_rollout_cbf_geometric", &half[s],
-                                             k > 1, h->cbf_chain_nominal && k < n_steps - 1, t + dt))
+                                             k > 1, k < n_steps - 1, t + dt))
             return rc;
         t += dt;
       }
@@ -2174,7 +2133,7 @@ int mds_rollout_cbf_geometric(mds_handle* h, double t0, int n_steps, void* obs, 
     if (k == 0) {
       if (int rc = mds_step_cbf_geometric(h, t0, obs, status, nullptr, stream)) return rc;   // validation; plain first step
     } else if (int rc = step_nominal_lowlevel(h, t0, obs, status, nullptr, stream, true, "mds_rollout_cbf_geometric", nullptr, k > 1,
-                                              h->cbf_chain_nominal && k < n_steps - 1, t0 + dt)) {
+                                              k < n_steps - 1, t0 + dt)) {
       return rc;
     }
     t0 += dt;
@@ -2241,7 +2200,7 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
   hipStream_t st = (hipStream_t)stream;
   // wavefronts per workgroup: 8 in fp32 (two workgroups per CU at <= 128 VGPRs); 4 in double (one wavefront per SIMD: the double
   // instantiation needs more than the 256 registers two wavefronts per SIMD would leave it)
-  constexpr int NWF = MDS_CBF_ROLL_NW, NWD = 4;
+  constexpr int NWF = 8, NWD = 4;
   const int nw = h->cfg.dtype == MDS_F64 ? NWD : NWF;
   // a workgroup owns 64 nw / Dp whole envs, Dp = the env width padded to 4, 8 or 16 lanes (any D <= 16)
   const int Dp = D <= 4 ? 4 : (D <= 8 ? 8 : 16), envs_per_wg = 64 * nw / Dp;
@@ -2261,14 +2220,6 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
       MDS_HIP(hipMalloc((void**)&stamps_dev, n_stamp * sizeof(unsigned long long) * ((n_steps + steps_per_launch - 1) / steps_per_launch)));
     }
   unsigned long long* const stamps_base = stamps_dev;
-  // tuning aid: MDS_TUNE_ROLL_EXTRA_LDS=<bytes> of unused dynamic LDS per workgroup (fewer workgroups per CU: occupancy experiments)
-  size_t extra_lds = 0;
-  if (const char* e = getenv("MDS_TUNE_ROLL_EXTRA_LDS")) {
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    if (end == e || *end != '\0' || v < 0 || v > 65536) return fail(MDS_EINVAL, "MDS_TUNE_ROLL_EXTRA_LDS: expected 0..65536 bytes");
-    extra_lds = (size_t)v;
-  }
   int slot = first_slot;
   double t = t0;
   for (int k0 = 0; k0 < n_steps; k0 += steps_per_launch) {
@@ -2282,8 +2233,8 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
     ra.last_rpm = (T*)rpm; ra.ll = (T*)h->ll; ra.pair_ij = h->pair_ij; ra.obstacles = (const T*)h->obstacles; ra.obs_log = (T*)obs_log;           \
     ra.slot = slot; ra.n_slots = log_slots > 0 ? log_slots : 1; ra.obs_last = (T*)obs; ra.status = (int*)status; ra.status_log = (int*)slog;      \
     ra.cost_io = h->cbf_cost; ra.max_iter = max_iter; ra.tol2 = (T)((TOL) * (TOL)); ra.tol = (T)(TOL); ra.stamps = stamps_dev;                   \
-    if (D == Dp) k_cbf_rollout<T, NOM, COMP, (sizeof(T) == 8 ? NWD : NWF), false><<<grid, 64 * nw, extra_lds, st>>>(ra);                          \
-    else k_cbf_rollout<T, NOM, COMP, (sizeof(T) == 8 ? NWD : NWF), true><<<grid, 64 * nw, extra_lds, st>>>(ra);                                   \
+    if (D == Dp) k_cbf_rollout<T, NOM, COMP, (sizeof(T) == 8 ? NWD : NWF), false><<<grid, 64 * nw, 0, st>>>(ra);                                  \
+    else k_cbf_rollout<T, NOM, COMP, (sizeof(T) == 8 ? NWD : NWF), true><<<grid, 64 * nw, 0, st>>>(ra);                                           \
   } while (0)
 #define MDS_CR_N(T, CC, CP, COMP, TOL)                        \
   do {                                                        \

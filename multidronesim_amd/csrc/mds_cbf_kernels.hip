@@ -368,10 +368,7 @@ template <int LO, int HI, typename F> __device__ __forceinline__ void desc_upto(
 
 // 3-way partition of the envs by last step's solve cost: order[c*E + k] = k-th env of class c, count[c].
 // One workgroup, coalesced strided passes (thread t owns envs t, t + kOrderThreads, ...).
-#ifndef MDS_ORDER_THREADS
-#define MDS_ORDER_THREADS 256
-#endif
-constexpr int kOrderThreads = MDS_ORDER_THREADS;   // one small workgroup: it has to find room on a CU beside the other chain's QP waves
+constexpr int kOrderThreads = 256;   // one small workgroup: it has to find room on a CU beside the other chain's QP waves
 __global__ __launch_bounds__(kOrderThreads) void k_cbf_order(const int E, const int* __restrict__ cost, int* __restrict__ order,
                                                     int* __restrict__ count) {
   __shared__ int wtot[3][kOrderThreads / 64];
@@ -434,23 +431,7 @@ template <typename T, int NV> struct CbfRow {
 // scratch.  ROWTAB: the selected row is fetched from an LDS copy of the rows (srow) by a uniform address; without it, from the owning
 // lane's registers (a select over its R rows + v_readlane) -- 16 bytes of LDS per row less.  Returns converged / iterations; su holds
 // the minimiser when converged.  Must be called with all 64 lanes active.
-// SMALLQ > 0 (thrust-only QPs, NV == 1): active sets of up to SMALLQ rows live in REGISTERS as wave-uniform values -- a row of this QP
-// has at most two coefficients, so everything a step needs of the active set (d = N^T a, the Gram matrix N^T N of <= 3 x 3, r = its
-// solve in closed form, the multipliers, the drop bookkeeping) is arithmetic on uniform operands that every lane runs alike: no Q, R
-// or multipliers in LDS, no column reads, no back-substitution chain of v_readlane, one wave reduction (|z|^2) per step instead of
-// three.  The step is the dual active-set step of the general path (solving the Gram system of the active normals directly, as the
-// plain-C checker of the tests does); a set that needs row SMALLQ + 1 is written out once as the thin QR the general path continues on.  The census of the C4
-// scenes: 0.76 tight pair rows per env-step on `under`, 2.6 iterations per env-step that iterates -- sets of 1-3 rows
-// are what the solver meets.  Unit-norm rows of this QP have coefficients +-1 (bounds) or +-1/sqrt2 (pairs): the Gram matrix of an
-// independent set is well conditioned (entries 0, +-1/2, +-1/sqrt2); should its determinant still come out tiny, the set is handed
-// to the QR path before the step is taken.
-#ifndef MDS_TUNE_HASZ
-#define MDS_TUNE_HASZ 1
-#endif
-#ifndef MDS_GI_SMALLQ
-#define MDS_GI_SMALLQ 0      // (measured on MI355X, round 4: 1 / 2 / 3 are 3 / 8 / 14 % SLOWER on C4 -- see DESIGN.md 4; kept for A/B)
-#endif
-template <typename T, int R, int NMAX, int NV, bool ROWTAB, int kQS, int SMALLQ = (NV == 1 ? MDS_GI_SMALLQ : 0)>
+template <typename T, int R, int NMAX, int NV, bool ROWTAB, int kQS>
 __device__ __forceinline__ void gi_solve(const int lane, const int n, const int max_iter, const T tol2, const bool infeasible0,
                                          const T (&ca)[R][NV], const T (&cb)[R][NV], const T (&b)[R], const int (&ia)[R], const int (&ib)[R],
                                          const bool (&valid)[R], bool (&act)[R], T* __restrict__ su, T* __restrict__ sd,
@@ -459,22 +440,9 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
                                          int& q_out) {
   constexpr bool PRE = NMAX * sizeof(T) <= 128;   // a lane's rows of Q and R fit in registers: one LDS round trip per step instead of 2q
   static_assert(kQS == (PRE ? ((NMAX + 3) / 4 * 4 + 4) : NMAX + 1), "LDS row stride of Q and R");
-  static_assert(SMALLQ >= 0 && SMALLQ <= 3 && (SMALLQ == 0 || NV == 1), "register-resident active sets: thrust-only QPs, at most 3 rows");
   bool converged = false;
   bool infeasible = infeasible0;
   int q = 0, it = 0;
-  // the register-resident active set (uniform): row k < q is  ra[k] u[ri[k]] + rb[k] u[rj[k]] <= .. (rb = 0, rj = ri on a one-variable
-  // row), multiplier rl[k], row id rid[k] (lane + 64 slot of the owner); g..: its Gram matrix
-  constexpr int QR = SMALLQ > 0 ? SMALLQ : 1;
-  bool small = SMALLQ > 0;
-  T ra[QR], rb[QR], rl[QR];
-  int ri[QR], rj[QR], rid[QR];
-  T g00 = T(1), g11 = T(1), g22 = T(1), g01 = T(0), g02 = T(0), g12 = T(0);
-#pragma unroll
-  for (int k = 0; k < QR; ++k) {
-    ra[k] = rb[k] = rl[k] = T(0);
-    ri[k] = rj[k] = rid[k] = 0;
-  }
   while (!infeasible && it < max_iter) {
     // ---- most violated row outside the active set (distance^2 to its half-space) ----
     T best = T(0);
@@ -515,7 +483,7 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
       converged = true;
       break;
     }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDS_TUNE_NO_SETPRIO)
+#if defined(__HIP_DEVICE_COMPILE__)
     // an env that iterates is on the launch's critical path (a serial chain of ~4 000-cycle steps, the envs that do not iterate
     // are throughput work): its wave takes the SIMD's issue slots first from here on
     __builtin_amdgcn_s_setprio(3);
@@ -573,149 +541,6 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
       for (int v = 0; v < NV; ++v) res = m_fma(wca[v], su[NV * wia + v], m_fma(two ? wcb[v] : T(0), su[NV * wib + v], res));
       const int ln = lane < NMAX ? lane : NMAX - 1;                                      // lanes >= n hold no row: clamp the address only
       const int lu = lane < n ? lane : n - 1;                                            // (u: inside this env's n variables -- past them lie another env's, which another wave may be writing)
-      if constexpr (SMALLQ > 0) {
-        if (small) {
-          const T my_u = su[lu];
-          const T na = wca[0], nb = two ? wcb[0] : T(0);
-          auto ncoef = [&](int v) { return (v == wia ? na : T(0)) + ((two && v == wib) ? nb : T(0)); };   // the new row's coefficient at variable v
-          // d = N^T a, r = (N^T N)^-1 d
-          T d[QR], r[QR];
-#pragma unroll
-          for (int k = 0; k < QR; ++k) {
-            d[k] = k < q ? m_fma(ra[k], ncoef(ri[k]), (rj[k] != ri[k]) ? rb[k] * ncoef(rj[k]) : T(0)) : T(0);
-            r[k] = T(0);
-          }
-          T det = T(1);
-          if (q == 1) {
-            det = g00;
-            r[0] = d[0] * m_rcp(g00);
-          } else if (QR >= 2 && q == 2) {
-            det = m_fma(g00, g11, -(g01 * g01));
-            const T id = m_rcp(det);
-            r[0] = m_fma(g11, d[0], -(g01 * d[QR >= 2 ? 1 : 0])) * id;
-            r[QR >= 2 ? 1 : 0] = m_fma(g00, d[QR >= 2 ? 1 : 0], -(g01 * d[0])) * id;
-          } else if (QR >= 3 && q == 3) {
-            constexpr int i1 = QR >= 3 ? 1 : 0, i2 = QR >= 3 ? 2 : 0;
-            const T c00 = m_fma(g11, g22, -(g12 * g12)), c01 = m_fma(g02, g12, -(g01 * g22)), c02 = m_fma(g01, g12, -(g02 * g11));
-            const T c11 = m_fma(g00, g22, -(g02 * g02)), c12 = m_fma(g01, g02, -(g00 * g12)), c22 = m_fma(g00, g11, -(g01 * g01));
-            det = m_fma(g00, c00, m_fma(g01, c01, g02 * c02));
-            const T id = m_rcp(det);
-            r[0] = m_fma(c00, d[0], m_fma(c01, d[i1], c02 * d[i2])) * id;
-            r[i1] = m_fma(c01, d[0], m_fma(c11, d[i1], c12 * d[i2])) * id;
-            r[i2] = m_fma(c02, d[0], m_fma(c12, d[i1], c22 * d[i2])) * id;
-          }
-          // a set at capacity, or a Gram determinant that rounding could own: continue on the thin QR in LDS (below)
-          if (q == SMALLQ || !(det > T(sizeof(T) == 4 ? 1e-3 : 1e-6))) {
-            for (int j = 0; j < q; ++j) {                                                // Gram-Schmidt append of row j, as the general step's
-              T ja = ra[0], jb = rb[0], jl = rl[0];
-              int ji = ri[0], jj = rj[0], jid = rid[0];
-#pragma unroll
-              for (int k = 1; k < QR; ++k)
-                if (k == j) { ja = ra[k]; jb = rb[k]; jl = rl[k]; ji = ri[k]; jj = rj[k]; jid = rid[k]; }
-              const bool jtwo = jj != ji;
-              T dcj = m_fma(ja, sQ[ji][ln], jtwo ? jb * sQ[jj][ln] : T(0));
-              dcj = lane < j ? dcj : T(0);
-              T zj = T(0);
-              if (lane < n) {
-                zj = (lane == ji ? ja : T(0)) + ((jtwo && lane == jj) ? jb : T(0));
-                for (int c = 0; c < j; ++c) zj = m_fma(-sQ[lane][c], wv::get(dcj, c), zj);
-              }
-              const T zzj = wv::allreduce_n<ROW0>(zj * zj, wv::Add());
-              const T inzj = m_rsqrt(zzj), nzj = zzj * inzj;
-              MDS_WAVE_SYNC();
-              if (lane < n) sQ[lane][j] = zj * inzj;
-              if (lane < j) sR[lane][j] = dcj;
-              if (lane == 0) {
-                sR[j][j] = nzj;
-                sdi[j] = inzj;
-                slam[j] = jl;
-                sact[j] = jid;
-              }
-              MDS_WAVE_SYNC();
-            }
-            small = false;
-          } else {
-            T zv = T(0);
-            if (lane < n) {
-              zv = ncoef(lane);
-#pragma unroll
-              for (int k = 0; k < QR; ++k)
-                if (k < q) zv = m_fma(-r[k], (lane == ri[k] ? ra[k] : T(0)) + ((rj[k] != ri[k] && lane == rj[k]) ? rb[k] : T(0)), zv);
-            }
-            const T zz = wv::allreduce_n<ROW0>(zv * zv, wv::Add());
-            T rmax = T(0);
-#pragma unroll
-            for (int k = 0; k < QR; ++k) rmax = k < q ? m_max(rmax, m_abs(r[k])) : rmax;
-            T t1 = GiEps<T>::inf;
-            int drop = 0;
-#pragma unroll
-            for (int k = 0; k < QR; ++k)
-              if (k < q && r[k] > GiEps<T>::r * rmax && r[k] > T(0)) {
-                const T cand = m_max(rl[k], T(0)) * m_rcp(r[k]);
-                if (cand < t1) {                                                         // ties: lowest column
-                  t1 = cand;
-                  drop = k;
-                }
-              }
-            // a set of n independent normals spans the space: whatever is left of z is rounding, and a 'full step' along it would add a
-            // DEPENDENT row (q > n: past the thin QR's columns -- found by the host emulation under UBSan on an fp32 order-3 env that then
-            // cycled to the iteration cap); only the dual step is possible there
-            const bool has_z = zz > GiEps<T>::z && (MDS_TUNE_HASZ != 1 || q < n);
-            const T t2 = has_z ? res * m_rcp(zz) : GiEps<T>::inf;
-            const T t = m_min(t1, t2);
-            if (!(t < GiEps<T>::inf)) {
-              infeasible = true;                                                         // no step possible: rows inconsistent
-              break;
-            }
-            const bool full = has_z && t2 <= t1;
-            MDS_WAVE_SYNC();
-            if (has_z && lane < n) su[lane] = m_fma(-t, zv, my_u);
-#pragma unroll
-            for (int k = 0; k < QR; ++k) rl[k] = k < q ? m_fma(-t, r[k], rl[k]) : rl[k];
-            lam_new += t;
-            if (full) {                                                                  // add: N <- [N a]
-              const T aa = m_fma(na, na, nb * nb);
-#pragma unroll
-              for (int k = 0; k < QR; ++k)
-                if (k == q) { ra[k] = na; rb[k] = nb; rl[k] = lam_new; ri[k] = wia; rj[k] = two ? wib : wia; rid[k] = wrow; }
-              if (q == 0) g00 = aa;
-              else if (q == 1) { g01 = d[0]; g11 = aa; }
-              else { g02 = d[0]; g12 = d[QR >= 2 ? 1 : 0]; g22 = aa; }
-              if (lane == owner) {
-#pragma unroll
-                for (int k = 0; k < R; ++k)
-                  if (k == kk) act[k] = true;
-              }
-              ++q;
-              MDS_WAVE_SYNC();
-              break;
-            }
-            // ---- drop active row `drop` (its multiplier reached zero) ----
-            int drow = rid[0];
-#pragma unroll
-            for (int k = 1; k < QR; ++k) drow = k == drop ? rid[k] : drow;
-            if (lane == (drow & 63)) {
-#pragma unroll
-              for (int k = 0; k < R; ++k)
-                if (k == (drow >> 6)) act[k] = false;
-            }
-            if (QR >= 3 && q == 3) {                                                     // the Gram matrix without row / column `drop`
-              if (drop == 0) { g00 = g11; g01 = g12; g11 = g22; }
-              else if (drop == 1) { g01 = g02; g11 = g22; }
-            } else if (q == 2 && drop == 0) {
-              g00 = g11;
-            }
-#pragma unroll
-            for (int k = 0; k + 1 < QR; ++k)
-              if (k >= drop) { ra[k] = ra[k + 1]; rb[k] = rb[k + 1]; rl[k] = rl[k + 1]; ri[k] = ri[k + 1]; rj[k] = rj[k + 1]; rid[k] = rid[k + 1]; }
-            --q;
-            MDS_WAVE_SYNC();
-            continue;
-          }
-        }
-        // (here: the set was just written out as a thin QR -- this step, same row and same count, runs on it below)
-      }
-#if !defined(MDS_TUNE_GI_NO_FIRST_STEP)
       if (q == 0) {
         // Empty active set (the first step of most solves, and the only one of more than half of them): the step runs along the
         // row's own normal -- no Q, R or multipliers to read, no blocking row, no back substitution.  The general step below with
@@ -755,7 +580,6 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
         MDS_WAVE_SYNC();
         break;
       }
-#endif
       T dc = T(0);
       {                                                                                  // d = Q^T a: read by every lane (clamped column) so that the
         T qa[NV], qb[NV];                                                                // reads join the step's one round trip, kept by lanes < q
@@ -819,9 +643,9 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
       const T t1 = wv::min_nonneg<ROW0>(t1v);
       const int drop = t1 < GiEps<T>::inf ? (int)__builtin_ctzll(__ballot(t1v == t1)) : 0;  // ties: lowest column
       // a set of n independent normals spans the space: whatever is left of z is rounding, and a 'full step' along it would add a
-            // DEPENDENT row (q > n: past the thin QR's columns -- found by the host emulation under UBSan on an fp32 order-3 env that then
-            // cycled to the iteration cap); only the dual step is possible there
-            const bool has_z = zz > GiEps<T>::z && (MDS_TUNE_HASZ != 1 || q < n);
+      // DEPENDENT row (q > n: past the thin QR's columns -- found by the host emulation under UBSan on an fp32 order-3 env that then
+      // cycled to the iteration cap); only the dual step is possible there
+      const bool has_z = zz > GiEps<T>::z && q < n;
       const T t2 = has_z ? res * m_rcp(zz) : GiEps<T>::inf;
       const T t = m_min(t1, t2);
       if (!(t < GiEps<T>::inf)) {
@@ -835,10 +659,6 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
       lam_new += t;
       if (!full) MDS_WAVE_SYNC();                                                        // the drop path reads slam / sact next; the add path only writes
       if (full) {                                                                        // add: N <- [N a]
-        if (MDS_TUNE_HASZ == 2 && q >= n) {
-          infeasible = true;
-          break;
-        }
         const T inz = m_rsqrt(zz), nz = zz * inz;
         if (lane < n) sQ[lane][q] = zv * inz;
         if (lane < q) sR[lane][q] = dc;
@@ -925,12 +745,6 @@ __device__ __forceinline__ void gi_solve(const int lane, const int n, const int 
 // NV = QP variables per agent (order 2: thrust only -> 1; order 3: yank, wx, wy -> 3, wz is box-only),
 // NMAX = compile-time bound on the number of QP variables n = NV * D (LDS footprint of Q, R ~ NMAX^2),
 // R = rows per lane.  One wavefront (= one env) per workgroup.
-#ifndef MDS_GI_ROWTAB
-#define MDS_GI_ROWTAB 1
-#endif
-#ifndef MDS_GI_MINWAVES
-#define MDS_GI_MINWAVES 1
-#endif
 // One env's QP on one wavefront (lane = threadIdx.x & 63, all 64 lanes active): its D x 20 observation block, D x xdim xdes block and
 // D x 4 nominal block in, its D x 4 u_safe block, status and iteration count out.  The blocks may live in global memory (k_cbf_filter_gi)
 // or in LDS (k_cbf_rollout_o3 stages them per control step); the LDS arrays of the solver are this function's own.
@@ -944,22 +758,15 @@ __device__ __forceinline__ void cbf_filter_env(const CbfParams<T>& P, const int 
   constexpr int kQS = PRE ? ((NMAX + 3) / 4 * 4 + 4) : NMAX + 1;   // LDS row stride: 16-byte rows (4 mod 16 dwords) / odd, both conflict-free column walks
   constexpr int DMAX = NMAX / NV;
   constexpr int NOBS_L = (DMAX * 20 + 63) / 64, NXD_L = (DMAX * XD + 63) / 64, NUN_L = (DMAX * 4 + 63) / 64;
-  static_assert(!MDS_GI_ROWTAB || sizeof(CbfRow<T, NV>) * R * 64 >= sizeof(S) * DMAX * 20, "raw obs staging aliases the row table");
+  static_assert(sizeof(CbfRow<T, NV>) * R * 64 >= sizeof(S) * DMAX * 20, "raw obs staging aliases the row table");
   __shared__ T sx[DMAX * XD], sxd[DMAX * XD];
   __shared__ T su[NMAX], sd[NMAX], slam[NMAX], sdi[NMAX];
   __shared__ T sQ[NMAX][kQS], sR[NMAX][kQS];
   __shared__ int sact[NMAX];
   __shared__ T sob[kCbfMaxObs * 4];
   __shared__ T swz[2][DMAX];
-#if MDS_GI_ROWTAB
   __shared__ __align__(16) CbfRow<T, NV> srow[R * 64];
-#else   // tuning build: no LDS copy of the rows (the selected row comes from its owner's registers); only the observation staging remains
-  __shared__ __align__(16) CbfRow<T, NV> srow[(sizeof(S) * DMAX * 20 + sizeof(CbfRow<T, NV>) - 1) / sizeof(CbfRow<T, NV>)];
-#endif
   S* sraw = reinterpret_cast<S*>(srow);                     // the env's observation rows, staged before the rows are built
-#if defined(MDS_TUNE_ITERS)
-  const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-#endif
   const int D = P.num_drones, n = NV * D;
   constexpr size_t base = 0;                    // (the pointers are this env's blocks)
   const int npairs = cbf_num_pairs(D), nobs_rows = D * P.n_obs, m = npairs + nobs_rows + 2 * n;
@@ -1103,25 +910,15 @@ __device__ __forceinline__ void cbf_filter_env(const CbfParams<T>& P, const int 
       }
       w.b = b[k];
       w.ij = ia[k] | (ib[k] << 8);
-#if MDS_GI_ROWTAB
       srow[r] = w;
-#endif
     }
   }
   MDS_WAVE_SYNC();
   bool converged = false;
   int q = 0, it = 0;
-  gi_solve<T, R, NMAX, NV, MDS_GI_ROWTAB != 0, kQS>(lane, n, max_iter, tol2, __any(bad), ca, cb, b, ia, ib, valid, act, su, sd, slam, sdi, sQ, sR, sact, srow,
+  gi_solve<T, R, NMAX, NV, true, kQS>(lane, n, max_iter, tol2, __any(bad), ca, cb, b, ia, ib, valid, act, su, sd, slam, sdi, sQ, sR, sact, srow,
                                       converged, it, q);
-#if defined(MDS_TUNE_ITERS)   // tuning build: iteration count and final active-set size in the high bits of status
-  {
-    const int nbox = __popcll(__ballot(lane < q && sact[lane < NMAX ? lane : 0] >= npairs + nobs_rows));
-    if (lane == 0) *status_env = (converged ? 0 : 1) | ((it & 0x7f) << 1) | ((q & 0x1f) << 8) | ((nbox & 0x1f) << 13) |
-                                 ((int)m_min<unsigned long long>((__builtin_amdgcn_s_memtime() - t_start) >> 8, 0x1fffull) << 18);
-  }
-#else
   if (lane == 0) *status_env = converged ? 0 : 1;
-#endif
   if (cost_env && lane == 0) *cost_env = it;
   MDS_WAVE_SYNC();
   // u_safe in the flat [D,4] layout of the nominal block that is still in registers
@@ -1147,7 +944,7 @@ __device__ __forceinline__ void cbf_filter_env(const CbfParams<T>& P, const int 
 }
 
 template <typename T, typename S, int R, int NMAX, int ORDER>
-__global__ __launch_bounds__(64, MDS_GI_MINWAVES) void k_cbf_filter_gi(const CbfParams<T> P, const int E, const T kf, const int* __restrict__ pair_ij,
+__global__ __launch_bounds__(64, 1) void k_cbf_filter_gi(const CbfParams<T> P, const int E, const T kf, const int* __restrict__ pair_ij,
                                                       const T* __restrict__ obstacles, const S* __restrict__ obs,
                                                       const S* __restrict__ xdes, const S* __restrict__ unom,
                                                       S* __restrict__ usafe, int* __restrict__ status, const int max_iter,
@@ -1163,11 +960,9 @@ __global__ __launch_bounds__(64, MDS_GI_MINWAVES) void k_cbf_filter_gi(const Cbf
     const int c0 = count_in[0], c1 = count_in[1];
     const int b = blockIdx.x;
     env = b < c0 ? order_in[b] : (b < c0 + c1 ? order_in[E + b - c0] : order_in[2 * E + b - c0 - c1]);
-#if !defined(MDS_TUNE_NO_SETPRIO)
     // the envs that iterated last time: on the critical path from their first instruction
     if (b < c0) __builtin_amdgcn_s_setprio(3);
     else if (b < c0 + c1) __builtin_amdgcn_s_setprio(2);
-#endif
   }
   if (env >= E) return;
   constexpr int XD = ORDER == 2 ? 9 : 10;
@@ -1410,53 +1205,32 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && R == 4) ? 4 : 1) void k_cbf_
 // (cbf_row_o2, the normalisation and reach test of cbf_o2_slot, gi_solve, the controller / physics templates).
 // t advances in double exactly like the host loop (t += CTRL_TIMESTEP, CBFTest.py:352).
 // ------------------------------------------------------------------------------------
-#ifndef MDS_CBF_ROLL_NW
-#define MDS_CBF_ROLL_NW 8
-#endif
 #ifndef MDS_ROLL_STAMPS
 #define MDS_ROLL_STAMPS 0       // 1: per-stage shader-clock stamps compiled in (profiles/tools/r03_stamps.sh builds such a library)
 #endif
-#ifndef MDS_TUNE_ROLL_PRIO_C
-#define MDS_TUNE_ROLL_PRIO_C 2     // issue priority of stages C and A (row build 0, scan / bookkeeping 1, an iterating solve 3); 0..3 measure within 2 % of each other
-#endif
-#ifndef MDS_TUNE_ROLL_SKIP
-#define MDS_TUNE_ROLL_SKIP 0   // tuning aid (cost breakdown of stage B): 1 no row polynomial, 2 no normalisation, 4 no scan / solve, 8 no rows
-#endif
-#ifndef MDS_ROLL_F64_WAVES
-#define MDS_ROLL_F64_WAVES 2      // waves per SIMD the float64 instantiation is compiled for (2: <= 256 VGPRs, two 4-wave workgroups per CU run side by side)
-#endif
-#ifndef MDS_ROLL_OBS_CHUNK
-#define MDS_ROLL_OBS_CHUNK 2
-#endif
-#ifndef MDS_ROLL_BOUNDS
-#define MDS_ROLL_BOUNDS 1      // 1: obstacle and thrust-box rows folded into per-drone bounds in the drone-per-lane stage (round 4); 0: round 3's row layout (A/B)
-#endif
 struct RollSlot {       // row r = lane + 64 k of any env: what it is, as the row build consumes it (built once per launch by roll_slot_of)
   int a0;               // barrier rows: byte offset of agent i's record half 0 from the env's first record (swizzle applied); else 0
-  int b0;               // pair rows: the same for agent j; other rows: byte offset of an obstacle record (obstacle o, or the first) in the
-                        // workgroup's LDS block
-  int ds;               // byte offset in the LDS block of -Ds^4: pair distance 2 safety_radius, or safety_radius + r_o
-  int kind;             // 0 none, 1 pair, 2 obstacle, 3 box row +u <= umax, 4 box row -u <= umax;  | agent i << 8 | agent j << 16 | pair << 24
+  int b0;               // pair rows: the same for agent j; other rows: byte offset of the first obstacle record in the workgroup's LDS
+                        // block (a harmless operand)
+  int ds;               // byte offset in the LDS block of -Ds^4 of the pair distance 2 safety_radius
+  int kind;             // 0 none, 1 pair, 3 bound row +u <= hi, 4 bound row -u <= -lo;  | agent i << 8 | agent j << 16 | pair << 24
 };
 
 // rec: record stride in bytes; swz: agents 8..15 keep their record halves swapped (16-byte halves, D = 16 only: see k_cbf_rollout);
 // sob / dso: byte offsets of the obstacle records and of the -Ds^4 table in the LDS block; wT: sizeof(T)
 template <typename T>
 __device__ __forceinline__ RollSlot roll_slot_of(const CbfParams<T>& P, const int* __restrict__ pair_ij, const int r, const int rec, const bool swz,
-                                                 const int sob, const int dso, const bool bounds = false) {
-  // bounds: the single-variable rows (obstacles, thrust box) are per-drone bounds made in stage A; the QP sees the pair rows, then
+                                                 const int sob, const int dso) {
+  // the single-variable rows (obstacles, thrust box) are per-drone bounds made in stage A; the QP sees the pair rows, then
   // D rows +u_var <= hi_var (kind 3) and D rows -u_var <= -lo_var (kind 4)
-  const int D = P.num_drones, npairs = cbf_num_pairs(D), nobs_rows = bounds ? 0 : D * P.n_obs, m = npairs + nobs_rows + 2 * D;
+  const int D = P.num_drones, npairs = cbf_num_pairs(D), m = npairs + 2 * D;
   auto half0 = [&](int ag) { return ag * rec + ((swz && ((ag >> 3) & 1)) ? 16 : 0); };
   RollSlot sl = {0, sob, dso, 0};
   if (r < npairs) {
     const int ij = pair_ij[r], ia = ij & 255, ib = ij >> 8;
     sl = {half0(ia), half0(ib), dso, 1 | (ia << 8) | (ib << 16) | (1 << 24)};
-  } else if (r < npairs + nobs_rows) {
-    const int q = r - npairs, ag = (q * P.obs_magic) >> 16, oo = q - ag * P.n_obs;       // as cbf_o2_slot
-    sl = {half0(ag), sob + oo * rec, dso + (1 + oo) * (int)sizeof(T), 2 | (ag << 8) | (ag << 16)};
   } else if (r < m) {
-    const int q = r - npairs - nobs_rows, var = q < D ? q : q - D;
+    const int q = r - npairs, var = q < D ? q : q - D;
     sl = {0, sob, dso, (q < D ? 3 : 4) | (var << 8) | (var << 16)};
   }
   return sl;
@@ -1532,12 +1306,12 @@ template <typename U> __device__ __forceinline__ U* lane_ptr(U* uniform_base, un
 
 // PAD: D is not 4, 8 or 16 -- an env is padded to the next of those widths (false: the padded and the real index coincide, and the
 // index arithmetic, the staging row and its guard fold away: the any-D form costs the C4 shape 2-3 %, measured).
+// The float64 instantiation is compiled for 2 waves per SIMD (<= 256 VGPRs, two 4-wave workgroups per CU run side by side).
 template <typename T, int NOM, bool COMP, int NW, bool PAD = true>
-__global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) void k_cbf_rollout(const RollArgs<T>) {
+__global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : 2) void k_cbf_rollout(const RollArgs<T>) {
 
   constexpr int NT = 64 * NW;
-  constexpr bool kBounds = MDS_ROLL_BOUNDS != 0;
-  constexpr int R = kBounds ? 3 : 4, NMAX = 16, NV = 1;            // rows per lane: 120 pair rows + 32 bound rows <= 192 (round 3: 216 rows)
+  constexpr int R = 3, NMAX = 16, NV = 1;                      // rows per lane: 120 pair rows + 32 bound rows <= 192 (round 3: 216 rows)
   constexpr int kQS = (NMAX + 3) / 4 * 4 + 4;
   constexpr int GBMAX = NT / 4;                                // envs per workgroup (D >= 4)
   // One drone's record: two 16-byte halves (px py e_pitch -e_roll | e_vx e_vy pz e_vz) -- the operand pairs of cbf_row_o2_pairs side
@@ -1571,12 +1345,12 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
   T* const sDs = reinterpret_cast<T*>(raw + kDsOff);                  // -Ds^4: [0] pairs, [1 + o] obstacle o
   __shared__ T st[14][NT];                                     // the state and u_hat[0] across stage B (lane-contiguous planes: conflict-free)
   __shared__ T su_all[NT];                                     // thrust variable of every drone: u_hat[0] in, QP minimiser out
-  // Per-drone bounds of the thrust variable (kBounds): every obstacle row (cbf/cbf.py:369-398) and the thrust box (:400-412) of order 2
+  // Per-drone bounds of the thrust variable: every obstacle row (cbf/cbf.py:369-398) and the thrust box (:400-412) of order 2
   // constrain u[4 i] of drone i alone and depend on drone i's own state only, so stage A -- one drone per lane, state in registers --
   // evaluates them and folds them into  u_i <= sbnd[0][i]  and  -u_i <= sbnd[1][i];  the QP of stage B sees the pair rows and these two
   // rows per drone.  An obstacle row beyond the reach of the box, or an empty interval, writes -inf to both: the env is infeasible
   // before any row of it is built.
-  __shared__ T sbnd[kBounds ? 2 : 1][kBounds ? NT : 1];
+  __shared__ T sbnd[2][NT];
   __shared__ __align__(16) RollSlot stab[R][64];               // row slot table
   __shared__ int sconv[GBMAX], scost[GBMAX], sorder[GBMAX];    // per env of the workgroup: QP solved; iterations of its last solve; hand-out order
   __shared__ int sticket;
@@ -1629,7 +1403,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
     const CbfParams<T> P = load_const(&a0->p.P);
     const T* obstacles = a0->obstacles;
   for (int r = tid; r < R * 64; r += NT)                       // (a loop: NW = 1 or 2 -- the host emulation of the tests -- has fewer threads than slots)
-    stab[r >> 6][r & 63] = roll_slot_of<T>(P, a0->pair_ij, r, kRec, kSwz && P.num_drones > 8, kSobOff, kDsOff, kBounds);
+    stab[r >> 6][r & 63] = roll_slot_of<T>(P, a0->pair_ij, r, kRec, kSwz && P.num_drones > 8, kSobOff, kDsOff);
   if (tid < kCbfMaxObs) {
     const bool on = tid < P.n_obs;
     for (int k = 0; k < 8; ++k) sobrec[tid][k] = T(0);
@@ -1651,7 +1425,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
   // The obstacle records and -Ds^4 written above are read by the FIRST stage A below (the per-drone bounds), by every wave: a workgroup
   // barrier per launch.  (Found by the host SIMT emulation of tests/emul/simt: without it the first control step of a launch raced --
   // round 3 read these tables in stage B only, behind the step's own barrier.)
-  if (kBounds) __syncthreads();
+  __syncthreads();
   T un1 = T(0), un2 = T(0), un3 = T(0);                        // u_hat[1..3] of this step (stage A -> stage C, in registers across stage B; [0]: st[13])
 
   // stage A of drone i on the state in registers at time ta: u_hat, the record, the stash of the state
@@ -1679,14 +1453,14 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
     const int sw = kSwz ? ((lq >> 3) & (Dp >> 4)) : 0;           // Dp = 16, agents 8..15: halves swapped
     *reinterpret_cast<V4*>(rc + 4 * sw) = V4{{s.p.x + Pl.cx, s.p.y + Pl.cy, rpy.y - T(0), -(rpy.x - T(0))}};
     *reinterpret_cast<V4*>(rc + 4 * (sw ^ 1)) = V4{{s.v.x - des.v.x, s.v.y - des.v.y, s.p.z + Pl.cz, s.v.z - des.v.z}};
-    if constexpr (kBounds) {
+    {
       // the drone's single-variable rows -> its bounds.  Same operands as round 3's obstacle row slots (an obstacle is a record with
-      // zero tracking errors: x - 0 is exact), same row polynomial (contraction off), four obstacles side by side.
+      // zero tracking errors: x - 0 is exact), same row polynomial (contraction off), kOb obstacles side by side.
       const CbfParams<T> Pb = load_const(&a->p.P);
       const T wx = s.p.x + Pl.cx, wy = s.p.y + Pl.cy, wz = s.p.z + Pl.cz, evx = s.v.x - des.v.x, evy = s.v.y - des.v.y, evz = s.v.z - des.v.z;
       T hi = Pb.umax[0], nlo = Pb.umax[0];
       bool badl = false;
-      constexpr int kOb = MDS_ROLL_OBS_CHUNK;                      // obstacle rows evaluated side by side (4: one scratch reload per step -- 128 VGPRs; 2: none)
+      constexpr int kOb = 2;                                       // obstacle rows evaluated side by side (4: one scratch reload per step -- 128 VGPRs; 2: none)
       for (int o0 = 0; o0 < Pb.n_obs; o0 += kOb) {                   // (uniform)
         Pair<T> exy[kOb], dpr[kOb], dvxy[kOb], ezvz[kOb];
         T nds4[kOb], hr[kOb], lg[kOb];
@@ -1738,7 +1512,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
     const Consts<T> c1 = load_const(&a0->p.c);
     stage_a(a0, c1, load_params(a0, (unsigned)i), t, tid);
   }
-  const int nbs = (cbf_num_pairs(D) + (kBounds ? 0 : D * a0->p.P.n_obs) + 63) >> 6;   // row slots that hold barrier rows
+  const int nbs = (cbf_num_pairs(D) + 63) >> 6;                // row slots that hold barrier rows
 
   for (int k = 0; k < n_steps; ++k) {
     if (wave == 0) {
@@ -1758,32 +1532,26 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
       if (lane == 0) sticket = 0;
     }
     if (kStamps && stamps != nullptr && k == 0) tk0 = __builtin_amdgcn_s_memtime();
-#if !(defined(MDS_TUNE_ROLL_NO_BAR) && (MDS_TUNE_ROLL_NO_BAR & 1))   // tuning aid: WRONG results (a race), only to bound what the barrier costs
     __syncthreads();
-#endif
     stamp(0);
 
     // ---- stage B: the workgroup's envs, one per wave at a time ----
     {
       Scratch& S = slice_of(wave).sc;
       if (kStamps && stamps != nullptr) tk1 = __builtin_amdgcn_s_memtime();
-#if !defined(MDS_TUNE_ROLL_STATIC)
-      // tickets are drawn one env ahead: the LDS atomic of the next env's ticket is in flight while this env's rows are built
+      // Envs go to the waves by ticket, not dealt round-robin: the static deal measured slower on every scene (MI355X, C4, us per
+      // control step, tickets -> static: far 29.5 -> 31.5, under 29.8 -> 31.9, level 41.2 -> 51.1) -- waves of a workgroup do not run
+      // at the same pace even when their envs cost the same, and the ticket absorbs it.
+      // Tickets are drawn one env ahead: the LDS atomic of the next env's ticket is in flight while this env's rows are built.
       int tk_next = 0;
       if (lane == 0) tk_next = atomicAdd(&sticket, 1);
       while (true) {
         const int tk = __builtin_amdgcn_readfirstlane(tk_next);
         if (tk >= nenv) break;                                     // wave-uniform
         if (lane == 0) tk_next = atomicAdd(&sticket, 1);
-#else
-      // A/B: the hand-out order dealt round-robin over the waves instead of the ticket counter (no LDS atomic per env).  Measured
-      // slower on every scene (MI355X, C4, us per control step, tickets -> static: far 29.5 -> 31.5, under 29.8 -> 31.9, level
-      // 41.2 -> 51.1): waves of a workgroup do not run at the same pace even when their envs cost the same, and the ticket absorbs it.
-      for (int tk = wave; tk < nenv; tk += NW) {
-#endif
         const int el = sorder[tk];                                 // env of the workgroup (uniform)
         stamp_b(6);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDS_TUNE_NO_SETPRIO)
+#if defined(__HIP_DEVICE_COMPILE__)
         __builtin_amdgcn_s_setprio(0);
 #endif
         // the CBF parameters of the row build: scalar loads per env (held across the solver they were spilled to VGPR lanes)
@@ -1799,15 +1567,12 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
         int ia[R], ib[R];
         bool vld[R], act[R];
         bool bad = false;
-        // kBounds: a drone whose single-variable rows leave no thrust value (stage A wrote -inf / -inf, or lo > hi) makes the env
-        // infeasible before any row is built -- the same decision as round 3's reach test while the rows were built, plus rows of one
-        // drone that contradict each other (round 3: found by the solver, "no step possible")
-        bool skip = false;
-        if constexpr (kBounds) {
-          const int lc = tl < D ? tl : D - 1;
-          const T h_l = sbnd[0][d0 + lc], n_l = sbnd[1][d0 + lc];
-          skip = __any(h_l + n_l < -ab->tol);
-        }
+        // a drone whose single-variable rows leave no thrust value (stage A wrote -inf / -inf, or lo > hi) makes the env infeasible
+        // before any row is built -- the same decision as round 3's reach test while the rows were built, plus rows of one drone that
+        // contradict each other (round 3: found by the solver, "no step possible")
+        const int lc = tl < D ? tl : D - 1;
+        const T h_l = sbnd[0][d0 + lc], n_l = sbnd[1][d0 + lc];
+        const bool skip = __any(h_l + n_l < -ab->tol);
         // Rows r = lane + 64 k.  Slots below NBS hold barrier rows -- all of them in slots below NBS - 1, beside the first box rows in
         // slot NBS - 1: ONE straight-line body per slot, every lane runs the barrier arithmetic (lanes of other kinds on a harmless
         // record pair, their result replaced by a select), all slots' LDS reads issued together (one round trip per env).
@@ -1819,14 +1584,12 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
         RollSlot sl[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) sl[r] = stab[r][tl];
-        T bndv[R];                                                 // kBounds: the right-hand side of a bound row (kind 3: hi, kind 4: -lo of its drone)
+        T bndv[R];                                                 // the right-hand side of a bound row (kind 3: hi, kind 4: -lo of its drone)
 #pragma unroll
         for (int r = 0; r < R; ++r) bndv[r] = P.umax[0];
-        if constexpr (kBounds) {
 #pragma unroll
-          for (int r = NBS - 1; r < R; ++r)
-            bndv[r] = (&sbnd[0][0])[(((sl[r].kind & 255) == 4) ? NT : 0) + d0 + ((sl[r].kind >> 8) & 255)];
-        }
+        for (int r = NBS - 1; r < R; ++r)
+          bndv[r] = (&sbnd[0][0])[(((sl[r].kind & 255) == 4) ? NT : 0) + d0 + ((sl[r].kind >> 8) & 255)];
         using P2 = Pair<T>;
         P2 oa[NBS][4], ob[NBS][4];                                 // operand pairs of agent i / agent j or obstacle: (px py) (e_pitch -e_roll) (e_vx e_vy) (pz e_vz)
         T nds4[NBS];
@@ -1860,14 +1623,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
           dvxy[r] = oa[r][2] - ob[r][2];
           ezvz[r] = oa[r][3] - ob[r][3];
         }
-#if (MDS_TUNE_ROLL_SKIP & 1)   // tuning aid: the row polynomial replaced by a sum of its operands (rows always satisfied)
-        for (int r = 0; r < NBS; ++r) {
-          hr[r] = T(100) + nds4[r] + exy[r].x + exy[r].y + dpr[r].x + dpr[r].y + dvxy[r].x + dvxy[r].y + ezvz[r].x + ezvz[r].y;
-          lg[r] = T(1);
-        }
-#else
         cbf_row_o2_pairs<T, NBS>(P, exy, dpr, dvxy, ezvz, nds4, hr, lg);
-#endif
         T cak[NBS], cbk[NBS], bk[NBS], n2[NBS], inv[NBS], reach[NBS];
         bool pos[NBS], unreachable[NBS];
 #define MDS_SLOTS(stmt)         \
@@ -1878,13 +1634,9 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
         } else {
           MDS_SLOTS(cbk[r] = pm[r] ? lg[r] : T(0))
         }
-#if (MDS_TUNE_ROLL_SKIP & 2)   // tuning aid: no normalisation
-        MDS_SLOTS(pos[r] = true; inv[r] = T(1); n2[r] = T(1))
-#else
         MDS_SLOTS(n2[r] = m_fma(cak[r], cak[r], cbk[r] * cbk[r]))
         MDS_SLOTS(pos[r] = n2[r] > T(0))
         MDS_SLOTS(inv[r] = pos[r] ? m_rsqrt(n2[r]) : T(1))
-#endif
         MDS_SLOTS(cak[r] *= inv[r])
         MDS_SLOTS(cbk[r] *= inv[r])
         MDS_SLOTS(bk[r] = hr[r] * inv[r])
@@ -1920,43 +1672,22 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
           }
         }
         };
-#if (MDS_TUNE_ROLL_SKIP & 8)   // tuning aid: no rows at all
-        for (int r = 0; r < R; ++r) { ca[r][0] = cb[r][0] = b[r] = T(0); ia[r] = ib[r] = 0; vld[r] = act[r] = false; }
-        if (false)
-#endif
         if (!skip) {
-          if constexpr (kBounds) {
-            if (__builtin_amdgcn_readfirstlane(nbs) <= 1) build_rows(wv::Ic<1>{});     // (wave-uniform; a scalar branch)
-            else build_rows(wv::Ic<2>{});
-          } else {
-            switch (__builtin_amdgcn_readfirstlane(nbs)) {
-              case 1: build_rows(wv::Ic<1>{}); break;
-              case 2: build_rows(wv::Ic<2>{}); break;
-              case 3: build_rows(wv::Ic<3>{}); break;
-              default: build_rows(wv::Ic<(R < 4 ? R : 4)>{}); break;
-            }
-          }
+          if (__builtin_amdgcn_readfirstlane(nbs) <= 1) build_rows(wv::Ic<1>{});       // (wave-uniform; a scalar branch)
+          else build_rows(wv::Ic<2>{});
         }
         stamp_b(7);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDS_TUNE_NO_SETPRIO)
+#if defined(__HIP_DEVICE_COMPILE__)
         // the scan, the bookkeeping and the next ticket are short serial chains (VALU -> scalar -> branch, LDS round trips): at equal
         // priority they queue behind the other waves' dense row arithmetic on every instruction; they go first, the row build yields
         __builtin_amdgcn_s_setprio(1);
 #endif
         bool converged = false;
         int it = 0, q = 0;
-#if (MDS_TUNE_ROLL_SKIP & 4)   // tuning aid: no scan, no solve (the rows are still built: their sum decides "converged")
-        {
-          T acc = T(0);
-          for (int r = 0; r < R; ++r) acc += ca[r][0] + cb[r][0] + b[r] + T(ia[r] + ib[r]) + (vld[r] ? T(1) : T(0));
-          converged = !__any(bad) && __any(acc > T(-1e30));
-        }
-        if (false)
-#endif
         if (!skip)
         gi_solve<T, R, NMAX, NV, false, kQS>(lane, D, max_iter, tol2, __any(bad), ca, cb, b, ia, ib, vld, act, &su_all[d0], S.sd, S.slam, S.sdi,
                                              S.sQ, S.sR, S.sact, nullptr, converged, it, q);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDS_TUNE_NO_SETPRIO)
+#if defined(__HIP_DEVICE_COMPILE__)
         __builtin_amdgcn_s_setprio(1);                             // (gi_solve raised it to 3 if the env iterated)
 #endif
         stamp_b(9);
@@ -1968,13 +1699,12 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
         stamp_b(8);
       }
     }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDS_TUNE_NO_SETPRIO)
-    __builtin_amdgcn_s_setprio(MDS_TUNE_ROLL_PRIO_C);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // issue priority of stages C and A: between the row build (0) and an iterating solve (3); 0..3 measure within 2 % of each other
+    __builtin_amdgcn_s_setprio(2);
 #endif
     stamp(1);
-#if !(defined(MDS_TUNE_ROLL_NO_BAR) && (MDS_TUNE_ROLL_NO_BAR & 2))   // tuning aid: WRONG results (a race), only to bound what the barrier costs
     __syncthreads();
-#endif
     stamp(2);
 
     // ---- stage C of this step, then stage A of the next: one drone per lane, state in registers ----
@@ -2116,15 +1846,12 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? 4 : MDS_ROLL_F64_WAVES) v
 // in the per-drone stages: the reference's order-3 scenes are a handful of drones -- but no launch, no u_hat / xdes / u_safe round
 // trip through HBM per control step.
 // ------------------------------------------------------------------------------------
-// The filter body is CALLED here, not inlined (MDS_TUNE_O3_CALL 1).  Inlined into this kernel's step loop, the float64 instantiation
+// The filter body is CALLED here, not inlined.  Inlined into this kernel's step loop, the float64 instantiation
 // (390 registers incl. 134 AGPRs) came out of the compiler wrong as soon as gi_solve was touched: with the q == n guard -- or with an
 // equivalent guard placed elsewhere -- step 0 was exact and every env's status wrong from step 1 on, while the same sources pass on the
 // host emulation under ASan / UBSan / TSan / MSan, the fp32 instantiation passes, and the step-by-step kernel (the same body, inlined
 // into a kernel without a loop around it) passes.  As a call the solver is compiled once per (T, R, NMAX) on its own registers; this
 // kernel is not a tuned path.
-#ifndef MDS_TUNE_O3_CALL
-#define MDS_TUNE_O3_CALL 1
-#endif
 template <typename T, int R, int NMAX>
 __device__ __noinline__ void cbf_filter_env_o3_call(const CbfParams<T>* P, int lane, T kf, const int* pair_ij, const T* obstacles, const T* obs, const T* xdes,
                                                     const T* unom, T* usafe, int* status_env, int max_iter, T tol2, int* cost_env) {
@@ -2167,11 +1894,7 @@ __global__ __launch_bounds__(64) void k_cbf_rollout_o3(const Consts<T> c, const 
       for (int j = 0; j < kObsDim; ++j) sobs[kObsDim * lane + j] = o[j];
     }
     MDS_WAVE_SYNC();
-#if MDS_TUNE_O3_CALL
     cbf_filter_env_o3_call<T, R, NMAX>(&P, lane, c.kf, pair_ij, obstacles, sobs, sxdes, sunom, susafe, &sres[0], max_iter, tol2, &sres[1]);
-#else
-    cbf_filter_env<T, T, R, NMAX, 3>(P, lane, c.kf, pair_ij, obstacles, sobs, sxdes, sunom, susafe, &sres[0], max_iter, tol2, &sres[1]);
-#endif
     MDS_WAVE_SYNC();
     if (lane == 0) {
       if (status_log) status_log[(size_t)k * E + env] = sres[0];
@@ -2398,7 +2121,7 @@ __global__ __launch_bounds__(64, sizeof(T) == 4 ? 3 : 1) void k_cbf_filter_q4(co
     if (rl < q && rc > GiEps<T>::r * rmax && rc > T(0)) t1v = m_max(my_lam, T(0)) * m_rcp(rc);
     const T t1 = r16::allreduce(t1v, wv::Min());
     const int drop = t1 < GiEps<T>::inf ? r16::first(t1v == t1, lane) : 0;
-    const bool has_z = zz > GiEps<T>::z && (MDS_TUNE_HASZ != 1 || q < n);                                                 // (q == n: only the dual step, as in gi_solve)
+    const bool has_z = zz > GiEps<T>::z && q < n;                                                 // (q == n: only the dual step, as in gi_solve)
     const T t2 = has_z ? res * m_rcp(zz) : GiEps<T>::inf;
     const T t = m_min(t1, t2);
     const bool nostep = stepping && !(t < GiEps<T>::inf);                                         // rows inconsistent: falls back

@@ -22,17 +22,12 @@ namespace mds {
 
 typedef _Float16 half_t;
 
-#ifndef MDS_KBLOCK
-#define MDS_KBLOCK 256
-#endif
-constexpr int kBlock = MDS_KBLOCK;
+constexpr int kBlock = 256;
 constexpr int kWave = 64;
 // minimum waves per SIMD requested from the register allocator for k_step (2nd __launch_bounds__
 // argument).  The fused kernel is left to the allocator: 78 VGPRs = 6 waves/SIMD without spills;
 // forcing 7 or 8 spills and measured 18 % slower.
-#ifndef MDS_STEP_MIN_WAVES
-#define MDS_STEP_MIN_WAVES 4
-#endif
+constexpr int kStepMinWaves = 4;
 
 template <typename S, typename T> __device__ __forceinline__ T ldp(const S* __restrict__ p, size_t i) { return (T)p[i]; }
 template <typename S, typename T> __device__ __forceinline__ void stp(S* __restrict__ p, size_t i, T v) { p[i] = (S)v; }
@@ -136,12 +131,8 @@ typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
 // (KEEP is a template argument on purpose: as a run-time flag the two stores sit in the arms of one branch, the optimiser merges them into a single
 // store and drops the non-temporal hint -- measured: form 1 15.6 -> 16.9 us per step, the 4 M-drone shard 135 -> 175, C5 8.4 -> 9.7)
 template <bool KEEP> __device__ __forceinline__ void store_chunk(v4u_t v, v4u_t* __restrict__ dst) {
-#if defined(MDS_TUNE_OBS_PLAIN_ALL)
-  *dst = v;
-#else
   if (KEEP) *dst = v;
   else __builtin_nontemporal_store(v, dst);          // write-once stream: non-temporal (measured +3..6 % on MI355X vs default-policy stores)
-#endif
 }
 // KEEP: default-policy stores instead of non-temporal ones -- for a destination that is REWRITTEN every control step
 // (the whole-rollout kernels with obs_every_step: the same [n, 20] array, 42 MB at config 3's size): the lines stay in the L2 / Infinity
@@ -151,18 +142,6 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
                                                bool valid, const T o[kObsDim]) {
   constexpr int kRowBytes = kObsDim * (int)sizeof(S);           // 80 / 160 / 40
   constexpr int kUnit = (kRowBytes % 16 == 0) ? 16 : 8;          // widest aligned LDS store per row
-#if defined(MDS_TUNE_OBS_DIRECT)   // tuning build: each lane stores its own row (strided 16-byte stores, no LDS)
-  if (valid) {
-    alignas(16) S row[kObsDim];
-    for (int k = 0; k < kObsDim; ++k) row[k] = (S)o[k];
-    unsigned char* dst = reinterpret_cast<unsigned char*>(obs) + (size_t)i * kRowBytes;
-    for (int k = 0; k < kRowBytes / kUnit; ++k) {
-      if (kUnit == 16) reinterpret_cast<uint4*>(dst)[k] = reinterpret_cast<const uint4*>(row)[k];
-      else reinterpret_cast<uint2*>(dst)[k] = reinterpret_cast<const uint2*>(row)[k];
-    }
-  }
-  return;
-#endif
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   unsigned char* lds_wave = lds_block + wave * (kWave * kRowBytes);
@@ -186,7 +165,6 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
   typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   constexpr int kIters = (kWave * kRowBytes + kWave * 16 - 1) / (kWave * 16);
   constexpr int kFull = (kWave * kRowBytes) / (kWave * 16);       // iterations in which all 64 lanes have a chunk of a full wave's rows
-#if !defined(MDS_TUNE_OBS_NO_FAST)
   if (rows >= kWave) {
     // a full wave (every wave but the shard's last): all LDS reads in flight at once, then the stores -- no per-chunk bounds test, one
     // LDS round trip instead of kIters serial ones
@@ -203,9 +181,7 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
         if (it < kFull || lane * 16 + 16 <= kWave * kRowBytes - it * kWave * 16)
             store_chunk<KEEP>(tmp[it - g], reinterpret_cast<v4u*>(gdst + (it * kWave + lane) * 16));
     }
-  } else
-#endif
-  if (rows > 0) {
+  } else if (rows > 0) {
     const int bytes = rows * kRowBytes;                          // multiple of 8; of 16 unless half with odd rows
     unsigned char* gdst = reinterpret_cast<unsigned char*>(obs) + (size_t)wave_base * kRowBytes;
     for (int it = 0; it < kIters; ++it) {
@@ -227,7 +203,7 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
 // [UPSTREAM] BaseAviary.step for every drone (a1-a4)
 // ------------------------------------------------------------------------------------
 template <typename T, typename S, bool HAS_OBS, bool RK4, bool DRAG, bool COMP = false>
-__global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && !COMP) ? MDS_STEP_MIN_WAVES : 1) void k_step(const Consts<T> c, const int n, const size_t ld, S* __restrict__ state,
+__global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && !COMP) ? kStepMinWaves : 1) void k_step(const Consts<T> c, const int n, const size_t ld, S* __restrict__ state,
                                                  const T* __restrict__ origin, T* __restrict__ last_rpm,
                                                  const S* __restrict__ action, S* __restrict__ obs, const int batch0,
                                                  S* __restrict__ state_lo = nullptr) {
@@ -474,10 +450,6 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
     T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4], act[4];
     if (DRAG)
       for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-#if defined(MDS_TUNE_NOCOMPUTE)   // timing-only build: memory traffic of the kernel without its arithmetic
-    for (int k = 0; k < 4; ++k) act[k] = clipped[k] = P.a + P.omega + P.yaw_rate + P.phase_shift + T(k);
-    s.p.x += T(1);
-#else
     {
       const Desired<T> des = lemniscate_local(P, t);
       const M3<T> R = quat_to_rot(s.q);
@@ -487,19 +459,10 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
       input_to_action(c, u, act);
     }
     aviary_step_any<T, RK4, DRAG, COMP>(c, s, in.r, act, prev, clipped);
-#endif
     if (DRAG || last_rpm)
       for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
     if (HAS_ACT) store4<S, T>(action_out + (size_t)i * 4, act);
-#if defined(MDS_TUNE_NOCOMPUTE)
-    if (HAS_OBS) {
-      o[0] = s.p.x + P.cx; o[1] = s.p.y + P.cy; o[2] = s.p.z + P.cz; o[3] = s.q[0]; o[4] = s.q[1]; o[5] = s.q[2]; o[6] = s.q[3];
-      o[7] = s.q[0]; o[8] = s.q[1]; o[9] = s.q[2]; o[10] = s.v.x; o[11] = s.v.y; o[12] = s.v.z; o[13] = s.w.x; o[14] = s.w.y; o[15] = s.w.z;
-      for (int k = 0; k < 4; ++k) o[16 + k] = clipped[k];
-    }
-#else
     if (HAS_OBS) pack_obs(s, V3<T>{P.cx, P.cy, P.cz}, clipped, o);
-#endif
   }
   // observation rows go out first (their LDS round trip must not sit behind the state stores)
   if (HAS_OBS) write_obs_rows<S, T>(lds, obs, n, i, valid, o);
@@ -511,11 +474,8 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
 
 // One batch of 256 drones per workgroup, inputs loaded straight into registers; every dtype / integrator / physics
 // combination is an instantiation of this kernel (the fp32 / Euler / DYN one is the bench's hot kernel).
-#ifndef MDS_GEOSIMPLE_MIN_WAVES
-#define MDS_GEOSIMPLE_MIN_WAVES 1
-#endif
 template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP = false>
-__global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4) ? MDS_GEOSIMPLE_MIN_WAVES : 1) void k_step_geometric(const Consts<T> c, const int n, const size_t ld, const double t,
+__global__ __launch_bounds__(kBlock, 1) void k_step_geometric(const Consts<T> c, const int n, const size_t ld, const double t,
                                                            S* __restrict__ state, const T* __restrict__ lem,
                                                            T* __restrict__ last_rpm, S* __restrict__ obs,
                                                            S* __restrict__ action_out, const int batch0,
@@ -661,11 +621,8 @@ __global__ void k_traj_eval(const int n, const double t, const SegTable segs, co
 // CTRL 0: GeometricControl; CTRL 1: the 12-state LQRController (K is only read then); CTRL 2 / 3: LQROmegaController +
 // ThrustOmegaController / LQRYankOmegaController + YankOmegaController (Kp then points at an LqrGain / LqrYoGain; the low level's
 // PID memory `ll` stays in registers for the whole rollout, the yank path's thrust state is the previous step's clipped RPM).
-#ifndef MDS_RG_MIN_WAVES
-#define MDS_RG_MIN_WAVES 1          // (A/B builds: waves per SIMD requested from the register allocator for the fp32 geometric instantiation)
-#endif
 template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0>
-__global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && CTRL == 0) ? MDS_RG_MIN_WAVES : 1) void k_rollout_geometric(const Consts<T> c, const void* __restrict__ Kp, const int n, const size_t ld, double t,
+__global__ __launch_bounds__(kBlock, 1) void k_rollout_geometric(const Consts<T> c, const void* __restrict__ Kp, const int n, const size_t ld, double t,
                                                               const double ctrl_dt, const int n_steps, S* __restrict__ state,
                                                               const T* __restrict__ lem, T* __restrict__ last_rpm,
                                                               S* __restrict__ obs_log, const size_t log_stride, S* __restrict__ obs_last,
@@ -690,25 +647,11 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && CTRL == 0) ? MDS
       if (CTRL == 3) load4<S, T>(obs_prev + (size_t)i * kObsDim + 16, clipped);      // calc_z_thrust(obs) of the first step
     }
   }
-#if defined(MDS_TUNE_RG)           // timing-only builds: 1 = the arithmetic without the observation rows, 2 = the rows without the arithmetic
-  T tune_acc = T(0);
-#endif
-#if defined(MDS_TUNE_RG_STAGGER)
-  for (int r = (int)((blockIdx.x >> MDS_TUNE_RG_STAGGER_SHIFT) & 3); r > 0; --r) __builtin_amdgcn_s_sleep(MDS_TUNE_RG_STAGGER);
-#endif
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     const bool want = obs_log != nullptr || (obs_last != nullptr && k == n_steps - 1);
-#if defined(MDS_TUNE_RG) && MDS_TUNE_RG == 2
-    if (valid) {
-      for (int j = 0; j < kObsDim; ++j) o[j] = in.s.p.x + T(j) * (T)t;
-    }
-    if (false) {
-      T act[4];
-#else
     if (valid) {
       T act[4];
-#endif
       {
         const Desired<T> des = lemniscate_local(in.P, t);
         T u[4];
@@ -733,21 +676,13 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && CTRL == 0) ? MDS
       else aviary_step<T, RK4, DRAG>(c, in.s, act, prev, clipped);
       if (want) pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
     }
-#if defined(MDS_TUNE_RG) && MDS_TUNE_RG == 1
-    if (valid && want)
-      for (int j = 0; j < kObsDim; ++j) tune_acc += o[j];
-#else
     if (obs_log != nullptr) {
       if (log_stride == 0) write_obs_rows<S, T, true>(lds, obs_log, n, i, valid, o);             // the same rows rewritten every step: keep them cached
       else write_obs_rows<S, T>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o);
     }
     if (obs_last != nullptr && k == n_steps - 1) write_obs_rows<S, T>(lds, obs_last, n, i, valid, o);
-#endif
     t += ctrl_dt;
   }
-#if defined(MDS_TUNE_RG)
-  if (valid && tune_acc == T(12345.678)) in.s.p.x += tune_acc;
-#endif
   if (valid) {
     store_state<S, T>(state, ld, i, in.s);
     if (state_lo) store_resid<S, T>(state_lo, ld, i, in.r);

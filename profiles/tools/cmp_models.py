@@ -1,6 +1,6 @@
 """mds_compare_models on a C3-sized observation log (524288 rows): microseconds per launch by HIP events, for several numbers of
 back-to-back launches (host enqueue time beside it).
-python3 profiles/tools/cmp_models.py [rows]        (MDS_TUNE_CMP_LDS=<bytes> limits the resident workgroups per CU)"""
+python3 profiles/tools/cmp_models.py [rows]"""
 import ctypes as C, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -31,7 +31,7 @@ fn = env._lib.mds_compare_models
 for _ in range(10):
     fn(*args)
 torch.cuda.synchronize(dev)
-res = {"rows": n, "pad": os.environ.get("MDS_TUNE_CMP_LDS", "0"), "dtype": str(obs.dtype)}
+res = {"rows": n, "dtype": str(obs.dtype)}
 for reps in (20, 50, 200, 1000):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(dev)
