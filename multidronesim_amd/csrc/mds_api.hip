@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <new>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -991,52 +992,83 @@ int mds_step_geometric(mds_handle* h, double t, void* obs, void* act, void* stre
   return MDS_OK;
 }
 
+extern "C++" {
+// The kernels take the compensated storage (COMP: MDS_F32C handles) and the destination of the rows (OBS) as template arguments.  The
+// fp32-arithmetic Euler / no-drag GeometricControl loops (the bench's headline among them) are instantiated per destination; the other
+// combinations (RK4, drag, the LQR family, float64) take it at run time (OBS -1), as before: their register budget is set by the
+// arithmetic, not by the three expansions of the row writer, and the library would otherwise carry three copies of each.
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP>
+static void launch_rollout_variant(mds_handle* h, const Consts<T>& C, const void* gain, double t0, double dt, int n_steps, void* obs_log, size_t log_stride,
+                                   void* obs_last, dim3 grid, hipStream_t st) {
+  constexpr bool kPerObs = sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0;
+  const int omode = obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog;
+#define MDS_ROLL(OBS)                                                                                                                         \
+  do {                                                                                                                                        \
+    if (h->traj_mode == 2) {   /* general trajectories: segment tables */                                                                     \
+      if constexpr (CTRL <= 1)                                                                                                                \
+        k_rollout_traj<T, S, RK4, DRAG, CTRL, COMP, OBS><<<grid, kBlock, 0, st>>>(C, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->origin, \
+                                                                                  SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm_track(h), (S*)obs_log, \
+                                                                                  log_stride, (S*)obs_last, (S*)h->state_lo);                  \
+    } else {                                                                                                                                  \
+      k_rollout_geometric<T, S, RK4, DRAG, CTRL, COMP, OBS><<<grid, kBlock, 0, st>>>(C, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, \
+                                                                                     (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last, (T*)h->ll, \
+                                                                                     (const S*)obs_last, (S*)h->state_lo);                      \
+    }                                                                                                                                         \
+  } while (0)
+  if constexpr (kPerObs) {
+    if (omode == kObsInPlace) MDS_ROLL(kObsInPlace);
+    else if (omode == kObsLog) MDS_ROLL(kObsLog);
+    else MDS_ROLL(kObsLast);
+  } else {
+    MDS_ROLL(-1);
+  }
+#undef MDS_ROLL
+}
+
 // One launch of the whole-rollout kernel: n_steps control steps with the state in registers.  ctrl: 0 GeometricControl, 1 LQRController
-// (12-state), 2 LQROmegaController + ThrustOmega, 3 LQRYankOmegaController + YankOmega.  Step k's observation goes to obs_log + k * log_stride
+// (12-state), 2 LQROmegaController + ThrustOmega, 3 LQRYankOmegaController + YankOmega (Lemniscate trajectories only, no fp16 storage:
+// rollout_fused has refused the rest).  Step k's observation goes to obs_log + k * log_stride
 // elements (log_stride = n * 20: a [n_steps, n, 20] log; 0: every step overwrites the same [n, 20] buffer, what a step-by-step loop with one
 // observation buffer does); obs_last (or NULL) receives the last step's.
-static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_steps, void* obs_log, size_t log_stride, void* obs_last, hipStream_t st) {
+template <typename T, typename S, int CTRL>
+static void launch_rollout_ctrl(mds_handle* h, const Consts<T>& C, double t0, int n_steps, void* obs_log, size_t log_stride, void* obs_last, hipStream_t st) {
   const dim3 grid = grid_for(h->n, kBlock);
   const double dt = 1.0 / h->cfg.ctrl_freq;
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
   // the gain (up to 48 values) is read from its device copy: passing it by value would not fit beside Consts in SGPRs
-  const void* gain = ctrl >= 1 ? h->gain_dev[ctrl - 1] : nullptr;
-#define MDS_ROLL(RK4, DRAG, CTRL)                                                                                                  \
-  MDS_DISPATCH(h, (k_rollout_geometric<T, S, RK4, DRAG, CTRL><<<grid, kBlock, 0, st>>>(C, gain, h->n, h->ld, t0, dt,                       \
-                                                                                       n_steps, (S*)h->state, (const T*)h->lem,       \
-                                                                                       (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last,   \
-                                                                                       (T*)h->ll, (const S*)obs_last, (S*)h->state_lo)))
-#define MDS_ROLLT(RK4, DRAG, CTRL)                                                                                                 \
-  MDS_DISPATCH(h, (k_rollout_traj<T, S, RK4, DRAG, CTRL><<<grid, kBlock, 0, st>>>(C, gain, h->n, h->ld, t0, dt,                                 \
-                                                                                  n_steps, (S*)h->state, (const T*)h->origin, SegTable{h->segs, h->nseg_total}, \
-                                                                                  h->tinfo, (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last, (S*)h->state_lo)))
-#define MDS_ROLL_C(CTRL)                                                    \
-  do {                                                                      \
-    if (h->traj_mode == 2) {   /* general trajectories: segment tables */   \
-      if (rk4 && drag) MDS_ROLLT(true, true, CTRL);                         \
-      else if (rk4) MDS_ROLLT(true, false, CTRL);                           \
-      else if (drag) MDS_ROLLT(false, true, CTRL);                          \
-      else MDS_ROLLT(false, false, CTRL);                                   \
-    } else if (rk4 && drag) MDS_ROLL(true, true, CTRL);                     \
-    else if (rk4) MDS_ROLL(true, false, CTRL);                              \
-    else if (drag) MDS_ROLL(false, true, CTRL);                             \
-    else MDS_ROLL(false, false, CTRL);                                      \
+  const void* gain = CTRL >= 1 ? h->gain_dev[CTRL - 1] : nullptr;
+#define MDS_ROLL_P(RK4, DRAG)                                                                                                                  \
+  do {                                                                                                                                         \
+    if constexpr (std::is_same_v<S, float>) {                                                                                                  \
+      if (is_comp(h)) {                                                                                                                        \
+        launch_rollout_variant<T, S, RK4, DRAG, CTRL, 1>(h, C, gain, t0, dt, n_steps, obs_log, log_stride, obs_last, grid, st);                \
+        break;                                                                                                                                 \
+      }                                                                                                                                        \
+    }                                                                                                                                          \
+    launch_rollout_variant<T, S, RK4, DRAG, CTRL, 0>(h, C, gain, t0, dt, n_steps, obs_log, log_stride, obs_last, grid, st);                    \
   } while (0)
-#define MDS_ROLL_LL(CTRL)                        \
-  do {                                           \
-    if (rk4 && drag) MDS_ROLL(true, true, CTRL); \
-    else if (rk4) MDS_ROLL(true, false, CTRL);   \
-    else if (drag) MDS_ROLL(false, true, CTRL);  \
-    else MDS_ROLL(false, false, CTRL);           \
-  } while (0)
-  if (ctrl == 3) MDS_ROLL_LL(3);
-  else if (ctrl == 2) MDS_ROLL_LL(2);
-  else if (ctrl == 1) MDS_ROLL_C(1);
+  if (rk4 && drag) MDS_ROLL_P(true, true);
+  else if (rk4) MDS_ROLL_P(true, false);
+  else if (drag) MDS_ROLL_P(false, true);
+  else MDS_ROLL_P(false, false);
+#undef MDS_ROLL_P
+}
+
+}  // extern "C++"
+
+static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_steps, void* obs_log, size_t log_stride, void* obs_last, hipStream_t st) {
+#define MDS_ROLL_C(CTRL) MDS_DISPATCH(h, (launch_rollout_ctrl<T, S, CTRL>(h, C, t0, n_steps, obs_log, log_stride, obs_last, st)))
+  if (ctrl == 3 || ctrl == 2) {
+    if (h->cfg.dtype == MDS_F64) {
+      if (ctrl == 3) launch_rollout_ctrl<double, double, 3>(h, h->cd, t0, n_steps, obs_log, log_stride, obs_last, st);
+      else launch_rollout_ctrl<double, double, 2>(h, h->cd, t0, n_steps, obs_log, log_stride, obs_last, st);
+    } else {
+      if (ctrl == 3) launch_rollout_ctrl<float, float, 3>(h, h->cf, t0, n_steps, obs_log, log_stride, obs_last, st);
+      else launch_rollout_ctrl<float, float, 2>(h, h->cf, t0, n_steps, obs_log, log_stride, obs_last, st);
+    }
+  } else if (ctrl == 1) MDS_ROLL_C(1);
   else MDS_ROLL_C(0);
-#undef MDS_ROLL_LL
 #undef MDS_ROLL_C
-#undef MDS_ROLLT
-#undef MDS_ROLL
 }
 
 int mds_rollout_geometric(mds_handle* h, double t0, int n_steps, void* obs, int obs_every_step, void* stream) {

@@ -249,15 +249,7 @@ __global__ __launch_bounds__(256) void k_cbf_filter_o2(const CbfParams<T> P, con
 
 // keeps two loaded values live at this point (an empty asm the optimiser cannot look through): used to stop it from sinking LDS
 // reads into the conditional code that consumes them
-// MDS_KEEP_V / MDS_KEEP_S: an empty asm the optimiser cannot look through, on a vector / scalar register value.  In a host build (the
-// SIMT emulation of tests/emul/simt: these kernels under AddressSanitizer on the CPU) they are no-ops.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MDS_KEEP_V(x) asm volatile("" : "+v"(x))
-#define MDS_KEEP_S(x) asm volatile("" : "+s"(x))
-#else
-#define MDS_KEEP_V(x) ((void)0)
-#define MDS_KEEP_S(x) ((void)0)
-#endif
+// (MDS_KEEP_V / MDS_KEEP_S: mds_kernels.hip)
 #define MDS_PIN2(a, b) \
   do {                 \
     MDS_KEEP_V(a);     \
@@ -1246,24 +1238,7 @@ template <typename T> struct RollParams {
   Consts<T> c;
   CbfParams<T> P;
 };
-#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
-#define MDS_CONST_AS __attribute__((address_space(4)))
-#else
-#define MDS_CONST_AS            // (host build of the SIMT emulation: a plain pointer)
-#endif
-// a by-value copy of a struct behind a constant-address-space pointer, word by word (the words that are used become scalar loads,
-// the others disappear)
-template <typename V> __device__ __forceinline__ V load_const(const V MDS_CONST_AS* p) {
-  static_assert(sizeof(V) % 4 == 0, "word-sized struct");
-  constexpr int N = (int)(sizeof(V) / 4);
-  const unsigned MDS_CONST_AS* w = reinterpret_cast<const unsigned MDS_CONST_AS*>(p);
-  unsigned tmp[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) tmp[k] = w[k];
-  V out;
-  __builtin_memcpy(&out, tmp, sizeof(V));
-  return out;
-}
+// (MDS_CONST_AS, load_const and lane_ptr: mds_kernels.hip)
 
 // The arguments of k_cbf_rollout, passed as ONE struct by value: the kernel never touches the parameter itself but reads the fields
 // through the kernarg segment pointer, made fresh per stage (fresh_args) -- scalar loads where a field is used, instead of 40 SGPRs
@@ -1294,14 +1269,6 @@ template <typename T> __device__ __forceinline__ const RollArgs<T> MDS_CONST_AS*
   const RollArgs<T> MDS_CONST_AS* p = (const RollArgs<T> MDS_CONST_AS*)__builtin_amdgcn_kernarg_segment_ptr();
   MDS_KEEP_S(p);
   return p;
-}
-
-// element idx of a per-lane plane behind a UNIFORM base pointer, addressed by a 32-bit byte offset: the access compiles to the
-// scalar-base + 32-bit-VGPR-offset form, one VGPR of address shared by every plane of the stage (64-bit per-lane addresses, one
-// pair per plane, are what the step loop of k_cbf_rollout spilled).  idx * sizeof(U) < 2^32: planes of at most 2^28 doubles.
-template <typename U> __device__ __forceinline__ U* lane_ptr(U* uniform_base, unsigned idx) {
-  using B = std::conditional_t<std::is_const_v<U>, const unsigned char, unsigned char>;
-  return reinterpret_cast<U*>(reinterpret_cast<B*>(uniform_base) + idx * (unsigned)sizeof(U));
 }
 
 // PAD: D is not 4, 8 or 16 -- an env is padded to the next of those widths (false: the padded and the real index coincide, and the

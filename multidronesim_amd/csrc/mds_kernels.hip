@@ -14,6 +14,7 @@
 //             span is written with 16-byte-per-lane, fully coalesced stores.
 // One drone per lane, 256 lanes per workgroup; no MFMA (no contraction wider than 4x4).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "mds_math.hpp"
 #include "mds_traj.hpp"
@@ -28,6 +29,59 @@ constexpr int kWave = 64;
 // argument).  The fused kernel is left to the allocator: 78 VGPRs = 6 waves/SIMD without spills;
 // forcing 7 or 8 spills and measured 18 % slower.
 constexpr int kStepMinWaves = 4;
+
+// MDS_KEEP_V / MDS_KEEP_S: an empty asm the optimiser cannot look through, on a vector / scalar register value: what is derived from
+// the value after this point is re-formed here instead of being hoisted out of a loop and held in registers across it.  In a host
+// build (the SIMT emulation of tests/emul/simt: these kernels under AddressSanitizer on the CPU) they are no-ops.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MDS_KEEP_V(x) asm volatile("" : "+v"(x))
+#define MDS_KEEP_S(x) asm volatile("" : "+s"(x))
+#else
+#define MDS_KEEP_V(x) ((void)0)
+#define MDS_KEEP_S(x) ((void)0)
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+#define MDS_CONST_AS __attribute__((address_space(4)))
+#else
+#define MDS_CONST_AS            // (host build of the SIMT emulation: a plain pointer)
+#endif
+// a by-value copy of a struct behind a constant-address-space pointer, word by word (the words that are used become scalar loads,
+// the others disappear)
+template <typename V> __device__ __forceinline__ V load_const(const V MDS_CONST_AS* p) {
+  static_assert(sizeof(V) % 4 == 0, "word-sized struct");
+  constexpr int N = (int)(sizeof(V) / 4);
+  const unsigned MDS_CONST_AS* w = reinterpret_cast<const unsigned MDS_CONST_AS*>(p);
+  unsigned tmp[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) tmp[k] = w[k];
+  V out;
+  __builtin_memcpy(&out, tmp, sizeof(V));
+  return out;
+}
+// element idx of a per-lane plane behind a UNIFORM base pointer, addressed by a 32-bit byte offset: the access compiles to the
+// scalar-base + 32-bit-VGPR-offset form, one VGPR of address shared by every plane (instead of a 64-bit per-lane address, one
+// register pair per plane).  idx * sizeof(U) < 2^32: planes of at most 2^28 doubles.
+template <typename U> __device__ __forceinline__ U* lane_ptr(U* uniform_base, unsigned idx) {
+  using B = std::conditional_t<std::is_const_v<U>, const unsigned char, unsigned char>;
+  return reinterpret_cast<U*>(reinterpret_cast<B*>(uniform_base) + idx * (unsigned)sizeof(U));
+}
+// a wave-uniform value the optimiser would otherwise carry in VGPRs (a double: there is no scalar f64 arithmetic): back into SGPRs
+__device__ __forceinline__ int uniform_i32(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane(x);
+#else
+  return x;
+#endif
+}
+__device__ __forceinline__ double uniform_f64(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+#else
+  return x;
+#endif
+}
 
 template <typename S, typename T> __device__ __forceinline__ T ldp(const S* __restrict__ p, size_t i) { return (T)p[i]; }
 template <typename S, typename T> __device__ __forceinline__ void stp(S* __restrict__ p, size_t i, T v) { p[i] = (S)v; }
@@ -137,13 +191,18 @@ template <bool KEEP> __device__ __forceinline__ void store_chunk(v4u_t v, v4u_t*
 // KEEP: default-policy stores instead of non-temporal ones -- for a destination that is REWRITTEN every control step
 // (the whole-rollout kernels with obs_every_step: the same [n, 20] array, 42 MB at config 3's size): the lines stay in the L2 / Infinity
 // Cache between the steps of a launch instead of going out to HBM each time (measured, C3, 2000 steps: 10.5 -> 8.6 us per control step).
-template <typename S, typename T, bool KEEP = false>
+// FRESH (the whole-rollout kernels, which call this once per step of a loop they never leave): the lane's LDS and global offsets and the
+// bound masks are formed from the thread index here, at every call, instead of being hoisted out of the step loop and held across it
+// (64-bit per-lane addresses and five masks per expansion); the wave's span is addressed as a scalar base + a 32-bit lane offset.
+template <typename S, typename T, bool KEEP = false, bool FRESH = false>
 __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_block, S* __restrict__ obs, int n, int i,
                                                bool valid, const T o[kObsDim]) {
   constexpr int kRowBytes = kObsDim * (int)sizeof(S);           // 80 / 160 / 40
   constexpr int kUnit = (kRowBytes % 16 == 0) ? 16 : 8;          // widest aligned LDS store per row
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
+  int tid = (int)threadIdx.x;
+  if (FRESH) MDS_KEEP_V(tid);
+  const int lane = tid & (kWave - 1);
+  const int wave = tid / kWave;
   unsigned char* lds_wave = lds_block + wave * (kWave * kRowBytes);
   if (valid) {
     alignas(16) S row[kObsDim];
@@ -160,7 +219,7 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int wave_base = i - lane;                                // first drone of this wave
+  const int wave_base = FRESH ? uniform_i32(i - lane) : i - lane;   // first drone of this wave
   const int rows = min(kWave, n - wave_base);                    // <= 0 for fully invalid waves
   typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   constexpr int kIters = (kWave * kRowBytes + kWave * 16 - 1) / (kWave * 16);
@@ -179,7 +238,7 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
 #pragma unroll
       for (int it = g; it < kIters && it < g + kGroup; ++it)
         if (it < kFull || lane * 16 + 16 <= kWave * kRowBytes - it * kWave * 16)
-            store_chunk<KEEP>(tmp[it - g], reinterpret_cast<v4u*>(gdst + (it * kWave + lane) * 16));
+            store_chunk<KEEP>(tmp[it - g], reinterpret_cast<v4u*>(gdst + (unsigned)((it * kWave + lane) * 16)));
     }
   } else if (rows > 0) {
     const int bytes = rows * kRowBytes;                          // multiple of 8; of 16 unless half with odd rows
@@ -621,20 +680,40 @@ __global__ void k_traj_eval(const int n, const double t, const SegTable segs, co
 // CTRL 0: GeometricControl; CTRL 1: the 12-state LQRController (K is only read then); CTRL 2 / 3: LQROmegaController +
 // ThrustOmegaController / LQRYankOmegaController + YankOmegaController (Kp then points at an LqrGain / LqrYoGain; the low level's
 // PID memory `ll` stays in registers for the whole rollout, the yank path's thrust state is the previous step's clipped RPM).
-template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0>
-__global__ __launch_bounds__(kBlock, 1) void k_rollout_geometric(const Consts<T> c, const void* __restrict__ Kp, const int n, const size_t ld, double t,
-                                                              const double ctrl_dt, const int n_steps, S* __restrict__ state,
-                                                              const T* __restrict__ lem, T* __restrict__ last_rpm,
-                                                              S* __restrict__ obs_log, const size_t log_stride, S* __restrict__ obs_last,
-                                                              T* __restrict__ ll = nullptr, const S* __restrict__ obs_prev = nullptr,
-                                                              S* __restrict__ state_lo = nullptr) {
+//
+// COMP (compensated storage: state_lo != NULL, MDS_F32C handles) and OBS (where the observation rows go) are compile-time for the
+// library's launches: as run-time flags every handle carried the 13 residuals across the loop, both integrators and three expansions
+// of write_obs_rows with their hoisted addresses and masks (125 VGPRs = 4 waves per SIMD for a step body that needs 53).  -1 = decided
+// from the arguments at run time: the form the host emulation (tests/emul/simt) instantiates, the same source either way.
+//   OBS kObsLast   : obs_log is not used; the last step's rows go to obs_last (if not NULL)
+//   OBS kObsInPlace: every step's rows rewrite obs_log (log_stride 0), default-policy stores (the lines stay cached between steps)
+//   OBS kObsLog    : step k's rows go to obs_log + k * log_stride, non-temporal stores; the last step's also to obs_last (if not NULL)
+// The step loop never ends, so whatever is invariant in it is hoisted and then lives in registers for good; the loop therefore
+// re-forms per step what costs a few instructions (products of the trajectory parameters and of the constants, the addresses),
+// reads the constants through the kernarg segment where they are used, and keeps the time in SGPRs.
+constexpr int kObsLast = 0, kObsInPlace = 1, kObsLog = 2;
+// waves per SIMD the register allocator is asked for: the fp32 Euler loops fit 6 (<= 80 VGPRs) without spilling; the others are left alone
+template <typename T, bool RK4, bool DRAG, int CTRL, int COMP, int OBS> constexpr int rollout_min_waves() {
+  return (sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0 && COMP == 0 && (OBS == kObsInPlace || OBS == kObsLog)) ? 6 : 1;
+}
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0, int COMP = -1, int OBS = -1>
+__global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP, OBS>())) void k_rollout_geometric(
+    const Consts<T> c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt, const int n_steps,
+    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
+    S* __restrict__ obs_last, T* __restrict__ ll = nullptr, const S* __restrict__ obs_prev = nullptr, S* __restrict__ state_lo = nullptr) {
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  const bool comp = COMP < 0 ? state_lo != nullptr : COMP != 0;
+  const int omode = OBS < 0 ? (obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog) : OBS;
+  // re-forming the loop's invariants per step pays where the register budget decides (Euler, plain storage: fp32 125 -> 71 VGPRs,
+  // float64 346 -> 233); the RK4 and compensated loops measured 1 % slower with it and keep their invariants hoisted
+  constexpr bool kLean = !RK4 && COMP != 1;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   const bool valid = i < n;
   GeoIn<T> in;
-  resid_zero(in.r);            // state_lo != NULL (MDS_F32C handles, a uniform branch): compensated accumulation, all 13 residuals in registers
-  if (valid && state_lo) load_resid<S, T>(state_lo, ld, i, in.r);
-  T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
+  resid_zero(in.r);            // compensated accumulation: all 13 residuals in registers (dead otherwise)
+  if (valid && comp) load_resid<S, T>(state_lo, ld, i, in.r);
+  T prev[4] = {T(0), T(0), T(0), T(0)};        // DRAG: the previous step's clipped RPM, as the drag term reads it
+  T thr[4] = {T(0), T(0), T(0), T(0)};         // CTRL 3: the same, as calc_z_thrust(obs) of the yank controller reads it
   LowLevelState<T> L;
   L.last_omega = L.integral = {T(0), T(0), T(0)};
   if (valid) {
@@ -644,15 +723,31 @@ __global__ __launch_bounds__(kBlock, 1) void k_rollout_geometric(const Consts<T>
     if (CTRL >= 2) {
       L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
       L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
-      if (CTRL == 3) load4<S, T>(obs_prev + (size_t)i * kObsDim + 16, clipped);      // calc_z_thrust(obs) of the first step
+      if (CTRL == 3) load4<S, T>(obs_prev + (size_t)i * kObsDim + 16, thr);      // calc_z_thrust(obs) of the first step
     }
   }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
-    const bool want = obs_log != nullptr || (obs_last != nullptr && k == n_steps - 1);
+    const bool last = k == n_steps - 1;
+    const bool want = omode != kObsLast || (obs_last != nullptr && last);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the constants: scalar loads through the kernarg segment (c_arg is the first argument), made fresh per step
+    const Consts<T> MDS_CONST_AS* cp = (const Consts<T> MDS_CONST_AS*)__builtin_amdgcn_kernarg_segment_ptr();
+    MDS_KEEP_S(cp);
+    const Consts<T> c = kLean ? load_const(cp) : c_arg;
+#else
+    const Consts<T>& c = c_arg;
+#endif
     if (valid) {
-      T act[4];
+      T act[4], clipped[4];
       {
+        // (per-lane parameters: what lemniscate_local derives from them is formed here every step, not held across the loop)
+        if (kLean) {
+          MDS_KEEP_V(in.P.a);
+          MDS_KEEP_V(in.P.omega);
+          MDS_KEEP_V(in.P.yaw_rate);
+          MDS_KEEP_V(in.P.phase_shift);
+        }
         const Desired<T> des = lemniscate_local(in.P, t);
         T u[4];
         if (CTRL == 0) {
@@ -665,29 +760,35 @@ __global__ __launch_bounds__(kBlock, 1) void k_rollout_geometric(const Consts<T>
         } else if (CTRL == 2) {
           lqr_omega_control<T>(c, *static_cast<const LqrGain<T>*>(Kp), euler_from_quat(in.s.q), in.s.v, in.s.p, des.p, des.v, des.yaw, u);
         } else {
-          lqr_yank_omega_control<T>(c, *static_cast<const LqrYoGain<T>*>(Kp), euler_from_quat(in.s.q), clipped, in.s.v, in.s.p, des.p, des.v,
+          lqr_yank_omega_control<T>(c, *static_cast<const LqrYoGain<T>*>(Kp), euler_from_quat(in.s.q), thr, in.s.v, in.s.p, des.p, des.v,
                                     des.yaw, u);
         }
         if (CTRL <= 1) input_to_action(c, u, act);
         else if (CTRL == 2) thrust_omega_control(c, (T)ctrl_dt, u, in.s.w, L, act);
-        else yank_omega_control(c, (T)ctrl_dt, u, clipped, in.s.w, L, act);
+        else yank_omega_control(c, (T)ctrl_dt, u, thr, in.s.w, L, act);
       }
-      if (state_lo) aviary_step_comp<T, RK4, DRAG>(c, in.s, in.r, act, prev, clipped);
+      if (comp) aviary_step_comp<T, RK4, DRAG>(c, in.s, in.r, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, in.s, act, prev, clipped);
+      if (CTRL == 3)
+        for (int j = 0; j < 4; ++j) thr[j] = clipped[j];
       if (want) pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
+      // the clipped RPM leaves with the last step (not carried to the end of the loop)
+      if (last && (DRAG || last_rpm)) {
+        unsigned iu = (unsigned)i;
+        MDS_KEEP_V(iu);                              // (the planes' addresses are formed here, not held across the loop)
+        for (int j = 0; j < 4; ++j) *lane_ptr(last_rpm + j * ld, iu) = DRAG ? prev[j] : clipped[j];
+      }
     }
-    if (obs_log != nullptr) {
-      if (log_stride == 0) write_obs_rows<S, T, true>(lds, obs_log, n, i, valid, o);             // the same rows rewritten every step: keep them cached
-      else write_obs_rows<S, T>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o);
-    }
-    if (obs_last != nullptr && k == n_steps - 1) write_obs_rows<S, T>(lds, obs_last, n, i, valid, o);
-    t += ctrl_dt;
+    if (omode == kObsInPlace) write_obs_rows<S, T, true, kLean>(lds, obs_log, n, i, valid, o);       // the same rows rewritten every step: keep them cached
+    else if (omode == kObsLog) write_obs_rows<S, T, false, kLean>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o);
+    if (omode != kObsInPlace && obs_last != nullptr && last) write_obs_rows<S, T, false, kLean>(lds, obs_last, n, i, valid, o);
+    t = uniform_f64(t + ctrl_dt);
   }
   if (valid) {
     store_state<S, T>(state, ld, i, in.s);
-    if (state_lo) store_resid<S, T>(state_lo, ld, i, in.r);
-    if (DRAG || (last_rpm && n_steps > 0))
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = DRAG ? prev[k] : clipped[k];
+    if (comp) store_resid<S, T>(state_lo, ld, i, in.r);
+    if (DRAG && n_steps <= 0)
+      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = prev[k];
     if (CTRL >= 2) {
       ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
       ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
@@ -696,7 +797,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_rollout_geometric(const Consts<T>
 }
 
 // The same whole-rollout loop for general trajectories (segment tables, evaluated in double every step like k_step_traj).
-template <typename T, typename S, bool RK4, bool DRAG, int CTRL>
+// COMP / OBS as in k_rollout_geometric.
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP = -1, int OBS = -1>
 __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, const void* __restrict__ Kp, const int n, const size_t ld, double t,
                                                          const double ctrl_dt, const int n_steps, S* __restrict__ state,
                                                          const T* __restrict__ origin, const SegTable segs,
@@ -704,15 +806,17 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
                                                          S* __restrict__ obs_log, const size_t log_stride, S* __restrict__ obs_last,
                                                          S* __restrict__ state_lo = nullptr) {
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  const bool comp = COMP < 0 ? state_lo != nullptr : COMP != 0;
+  const int omode = OBS < 0 ? (obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog) : OBS;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   const bool valid = i < n;
   State<T> s;
   Resid<T> r;
   resid_zero(r);
-  if (valid && state_lo) load_resid<S, T>(state_lo, ld, i, r);
+  if (valid && comp) load_resid<S, T>(state_lo, ld, i, r);
   V3<T> org = {T(0), T(0), T(0)};
   TrajInfo ti = {0, 1, 0, 0};
-  T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
+  T prev[4] = {T(0), T(0), T(0), T(0)};        // DRAG: the previous step's clipped RPM
   if (valid) {
     load_state<S, T>(state, ld, i, s);
     org = {origin[i], origin[ld + i], origin[2 * ld + i]};
@@ -722,10 +826,11 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
   }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
-    const bool want = obs_log != nullptr || (obs_last != nullptr && k == n_steps - 1);
+    const bool last = k == n_steps - 1;
+    const bool want = omode != kObsLast || (obs_last != nullptr && last);
     if (valid) {
       const Desired<T> des = TrajLocal<T>::eval(segs, ti, t, org);
-      T u[4], act[4];
+      T u[4], act[4], clipped[4];
       if (CTRL == 0) {
         const M3<T> R = quat_to_rot(s.q);
         geometric_control<T>(c, s.p - des.p, R, s.v, mul(R, s.w), des, u, nullptr);
@@ -734,22 +839,25 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
                          des.yaw_rate, u);
       }
       input_to_action(c, u, act);
-      if (state_lo) aviary_step_comp<T, RK4, DRAG>(c, s, r, act, prev, clipped);
+      if (comp) aviary_step_comp<T, RK4, DRAG>(c, s, r, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, s, act, prev, clipped);
       if (want) pack_obs(s, org, clipped, o);
+      if (last && (DRAG || last_rpm)) {              // the clipped RPM leaves with the last step (not carried to the end of the loop)
+        unsigned iu = (unsigned)i;
+        MDS_KEEP_V(iu);
+        for (int j = 0; j < 4; ++j) *lane_ptr(last_rpm + j * ld, iu) = DRAG ? prev[j] : clipped[j];
+      }
     }
-    if (obs_log != nullptr) {
-      if (log_stride == 0) write_obs_rows<S, T, true>(lds, obs_log, n, i, valid, o);             // the same rows rewritten every step: keep them cached
-      else write_obs_rows<S, T>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o);
-    }
-    if (obs_last != nullptr && k == n_steps - 1) write_obs_rows<S, T>(lds, obs_last, n, i, valid, o);
-    t += ctrl_dt;
+    if (omode == kObsInPlace) write_obs_rows<S, T, true, true>(lds, obs_log, n, i, valid, o);       // the same rows rewritten every step: keep them cached
+    else if (omode == kObsLog) write_obs_rows<S, T, false, true>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o);
+    if (omode != kObsInPlace && obs_last != nullptr && last) write_obs_rows<S, T, false, true>(lds, obs_last, n, i, valid, o);
+    t = uniform_f64(t + ctrl_dt);
   }
   if (valid) {
     store_state<S, T>(state, ld, i, s);
-    if (state_lo) store_resid<S, T>(state_lo, ld, i, r);
-    if (DRAG || (last_rpm && n_steps > 0))
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = DRAG ? prev[k] : clipped[k];
+    if (comp) store_resid<S, T>(state_lo, ld, i, r);
+    if (DRAG && n_steps <= 0)
+      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = prev[k];
   }
 }
 

@@ -229,16 +229,18 @@ template <typename T> MDS_HD void quat_from_euler(T roll, T pitch, T yaw, T q[4]
 template <typename T> MDS_HD V3<T> euler_from_quat(const T q[4]) {
   const T x = q[0], y = q[1], z = q[2], w = q[3];
   const T sqx = x * x, sqy = y * y, sqz = z * z, squ = w * w;
-  const T sarg = T(-2) * (x * z - w * y);
+  // (the three sums of two products below are written with the FMA the compiler picks for them in the step kernels: left to
+  // contraction, which of the two products is rounded first differs from one kernel to the next, and with it the last bit of the angle)
+  const T sarg = T(-2) * m_fma(x, z, -(w * y));
   V3<T> rpy;
   if (sarg <= T(-0.99999)) {
     rpy = {T(0), T(-1.57079632679489661923), T(2) * m_atan2(x, -y)};
   } else if (sarg >= T(0.99999)) {
     rpy = {T(0), T(1.57079632679489661923), T(2) * m_atan2(-x, y)};
   } else {
-    rpy.x = m_atan2(T(2) * (y * z + w * x), squ - sqx - sqy + sqz);
+    rpy.x = m_atan2(T(2) * m_fma(y, z, w * x), squ - sqx - sqy + sqz);
     rpy.y = m_asin(sarg);
-    rpy.z = m_atan2(T(2) * (x * y + w * z), squ + sqx - sqy - sqz);
+    rpy.z = m_atan2(T(2) * m_fma(w, z, x * y), squ + sqx - sqy - sqz);
   }
   return rpy;
 }
