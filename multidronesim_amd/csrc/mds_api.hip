@@ -88,39 +88,49 @@ __global__ void k_noop() {}
 
 }  // namespace
 
+// Everything the host prepares once per compute type T and passes to kernels by value.  The handle keeps a float and a double instance
+// (params<T>(h)): the setters fill both, a launch takes the one of its dtype.
+template <typename T> struct HostParams {
+  Consts<T> c;
+  EnvFx<T> fx;
+  CbfParams<T> cbf;
+  DslPidGains<T> pid;
+  LqrGain<T> lqr;
+  LqrYoGain<T> lqr_yo;
+  Lqr12Gain<T> lqr12;
+};
+
 struct mds_handle {
-  mds_config cfg;
-  mds_geometric_gains gains;
-  double wind[3];
-  int n;
-  size_t ld;           // plane stride (elements)
-  void* state;         // S [13][ld]
+  mds_config cfg = {};
+  mds_geometric_gains gains = {};
+  double wind[3] = {0.0, 0.0, 0.0};
+  int n = 0;
+  size_t ld = 0;                 // plane stride (elements)
+  void* state = nullptr;         // S [13][ld]
   void* state_lo = nullptr;      // MDS_F32C: float [ld][4] = residuals of the three body rates + pad (load_resid in mds_kernels.hip)
-  void* origin;        // T [3][ld]
-  void* last_rpm;      // T [4][ld]
-  void* lem;           // T [7][ld]
-  double* scratch;     // double [n*20] device staging for host<->device set-up calls
+  void* origin = nullptr;        // T [3][ld]
+  void* last_rpm = nullptr;      // T [4][ld]
+  void* lem = nullptr;           // T [7][ld]
+  double* scratch = nullptr;     // double [n*20] device staging for host<->device set-up calls
   double* init_pose = nullptr;   // double [n*6]: xyz, rpy of the last mds_reset (episode resets on the device, mds_reset_async)
-  bool has_traj;
-  int traj_mode;        // 1: per-drone Lemniscate planes (fused fp32 fast path), 2: general segment tables
-  double* segs;         // device [MDS_SEG_DIM, total]: field-major (mds_traj.hpp SegTable)
+  bool has_traj = false;
+  int traj_mode = 0;             // 1: per-drone Lemniscate planes (fused fp32 fast path), 2: general segment tables
+  double* segs = nullptr;        // device [MDS_SEG_DIM, total]: field-major (mds_traj.hpp SegTable)
   int nseg_total = 0;
-  int* tinfo;           // device [n, 3] = first segment, nseg | compound << 16, stride between pieces (mds_traj.hpp TrajInfo)
-  Consts<float> cf;
-  Consts<double> cd;
+  int* tinfo = nullptr;          // device [n, 3] = first segment, nseg | compound << 16, stride between pieces (mds_traj.hpp TrajInfo)
+  HostParams<float> p32 = {};
+  HostParams<double> p64 = {};
   // ECBF filter
-  bool has_cbf;
-  mds_cbf_params cbf;
-  CbfParams<float> cbf_f;
-  CbfParams<double> cbf_d;
-  int* pair_ij;        // device [D(D-1)/2]
-  void* obstacles;     // device T [n_obs,4]
+  bool has_cbf = false;
+  mds_cbf_params cbf = {};
+  int* pair_ij = nullptr;        // device [D(D-1)/2]
+  void* obstacles = nullptr;     // device T [n_obs,4]
   // slot 0: the whole batch; slots 1, 2: the two env halves of mds_rollout_cbf_geometric (each keeps its own cost classes)
-  int* cbf_order;      // [3 slots][3,E] env ids by cost class (longest-first dispatch of the QP kernel)
-  int* cbf_count;      // [3 slots][4]
+  int* cbf_order = nullptr;      // [3 slots][3,E] env ids by cost class (longest-first dispatch of the QP kernel)
+  int* cbf_count = nullptr;      // [3 slots][4]
   int cbf_calls_half[2] = {-1, -1};
-  int* cbf_cost;       // [E] GI iterations of the last launch
-  int cbf_calls;       // launches since the classes were rebuilt; -1: no classes yet
+  int* cbf_cost = nullptr;       // [E] GI iterations of the last launch
+  int cbf_calls = -1;            // launches since the classes were rebuilt; -1: no classes yet
   int rollout_streams = 0;              // mds_set_rollout_streams: 0 auto, 1, 2
   // two-chain rollouts: chain 0 runs on the caller's stream, chain 1 on this internal stream; ev[0] forks it off the caller's
   // stream, ev[1] joins it back.  Created (and primed) by mds_create for shards that can split, else by mds_set_rollout_streams(h, 2).
@@ -139,36 +149,32 @@ struct mds_handle {
   bool cbf_step_persistent = false;     // mds_cbf_set_step_kernel(h, 2): a CBF-filtered step = one launch of the persistent rollout kernel where it applies
   bool cbf_fused = false;               // mds_cbf_set_step_kernel / MDS_CBF_FUSED=1 at configure time: the one-launch CBF step (k_cbf_step) where it applies; it wins only
                                         // on scenes whose QPs need no iterations (see the kernel's header), so the default is the three launches
-  void* cbf_unom;      // S [n,4]  scratch of mds_step_cbf_geometric
-  void* cbf_xdes;      // S [n,9]
-  void* cbf_usafe;     // S [n,4]
-  void* ll;            // T [6][ld]: ThrustOmega last_omega3 | integral3
-  void* pid;           // T [9][ld]: DSLPID last_rpy3 | integral_pos_e3 | integral_rpy_e3
-  DslPidGains<float> pid_f;
-  DslPidGains<double> pid_d;
-  bool has_lqr;
-  int cbf_nominal;     // 0 geometric, 1 lqr-omega, 2 lqr-yank-omega (order 3)
-  LqrGain<float> lqr_f;
-  LqrGain<double> lqr_d;
-  bool has_lqr_yo;
-  LqrYoGain<float> lqr_yo_f;
-  LqrYoGain<double> lqr_yo_d;
-  bool has_lqr12;
-  void* gain_dev[3];   // device copies of the gains for the whole-rollout kernels: 0 LQR-12, 1 LQR-omega, 2 LQR-yank-omega (written by the mds_set_*_gain calls)
-  Lqr12Gain<float> lqr12_f;
-  Lqr12Gain<double> lqr12_d;
-  void* state_alt;     // second state buffer of the ground-effect / downwash step (double-buffered substeps)
+  void* cbf_unom = nullptr;      // S [n,4]  scratch of mds_step_cbf_geometric
+  void* cbf_xdes = nullptr;      // S [n,9]
+  void* cbf_usafe = nullptr;     // S [n,4]
+  void* ll = nullptr;            // T [6][ld]: ThrustOmega last_omega3 | integral3
+  void* pid = nullptr;           // T [9][ld]: DSLPID last_rpy3 | integral_pos_e3 | integral_rpy_e3
+  bool has_lqr = false;
+  int cbf_nominal = 0;           // 0 geometric, 1 lqr-omega, 2 lqr-yank-omega (order 3)
+  bool has_lqr_yo = false;
+  bool has_lqr12 = false;
+  // device copies of the gains for the whole-rollout kernels: 0 LQR-12, 1 LQR-omega, 2 LQR-yank-omega (written by the mds_set_*_gain calls)
+  void* gain_dev[3] = {nullptr, nullptr, nullptr};
+  void* state_alt = nullptr;     // second state buffer of the ground-effect / downwash step (double-buffered substeps)
   void* act_scratch = nullptr;   // S [n,4]: the controller's action, replayed by the later substeps of a ground-effect / downwash step
-  bool envfx;          // physics has ground effect and / or downwash
-  EnvFx<float> fx_f;
-  EnvFx<double> fx_d;
+  bool envfx = false;            // physics has ground effect and / or downwash
   // FedCE / dLQR (mds_fedce_*, mds_*dlqr*): per-drone RLS state in float64, per-env gain in the compute type
   double* fedce_P = nullptr;      // [n][16][16]
   double* fedce_theta = nullptr;  // [n][12]: the free entries of theta (mds_fedce_kernels.hip)
   void* dlqr_K = nullptr;         // T [E][4][12 D][D] (dlqr_kidx)
-  bool track_rpm;      // last_rpm planes maintained by every step kernel (DYN_DRAG, order-3 CBF, or cfg.track_last_rpm)
-  bool rpm_stale;      // a step ran without tracking since the last reset
+  bool track_rpm = false;        // last_rpm planes maintained by every step kernel (DYN_DRAG, order-3 CBF, or cfg.track_last_rpm)
+  bool rpm_stale = false;        // a step ran without tracking since the last reset
 };
+
+template <typename T> static inline const HostParams<T>& params(const mds_handle* h) {
+  if constexpr (sizeof(T) == 8) return h->p64;
+  else return h->p32;
+}
 
 static inline bool has_drag(const mds_handle* h) {
   return h->cfg.physics == MDS_PHYSICS_DYN_DRAG || h->cfg.physics == MDS_PHYSICS_DYN_GND_DRAG_DW;
@@ -272,22 +278,47 @@ static int split_join(mds_handle* h, hipStream_t st, int rc_body) {
   return rc;
 }
 
-// dispatch on the handle dtype: F32 -> <float,float>, F64 -> <double,double>, F16 -> <float,half_t>
-#define MDS_DISPATCH(h, EXPR)                                               \
-  do {                                                                      \
-    if ((h)->cfg.dtype == MDS_F32 || (h)->cfg.dtype == MDS_F32C) {           \
-      typedef float T; typedef float S; const Consts<T>& C = (h)->cf; (void)C; EXPR; \
-    } else if ((h)->cfg.dtype == MDS_F64) {                                 \
-      typedef double T; typedef double S; const Consts<T>& C = (h)->cd; (void)C; EXPR; \
-    } else {                                                                \
-      typedef float T; typedef half_t S; const Consts<T>& C = (h)->cf; (void)C; EXPR; \
-    }                                                                       \
-  } while (0)
+// Run-time handle state -> template arguments.  Each helper calls a generic lambda with compile-time tags, so that a launch (its kernel
+// name and argument list) is written once, in ordinary code, inside the lambda.  They instantiate exactly the branches listed here.
+// with_flags(f, a, b, ...): f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...)
+template <typename F> static void with_flags(F&& f) { f(); }
+template <typename F, typename... Rest> static void with_flags(F&& f, bool b, Rest... rest) {
+  if (b) with_flags([&](auto... r) { f(std::true_type{}, r...); }, rest...);
+  else with_flags([&](auto... r) { f(std::false_type{}, r...); }, rest...);
+}
+// with_int<V0, V1, ...>(v, f): f(std::integral_constant<int, Vk>{}) for the Vk equal to v (the last one listed when none is)
+template <int V, int... Vs, typename F> static void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+  else if (v == V) f(std::integral_constant<int, V>{});
+  else with_int<Vs...>(v, f);
+}
+// dtype tag: T the compute type, S the storage type, COMP the compensated fp32 storage of MDS_F32C handles (fp32 buffers + state_lo)
+template <typename T_, typename S_, bool COMP_ = false> struct DType {
+  using T = T_;
+  using S = S_;
+  static constexpr bool COMP = COMP_;
+};
+// with_dtype: every dtype of mds.h, fp16 storage included (float arithmetic on half_t buffers)
+template <typename F> static void with_dtype(int dtype, F&& f) {
+  if (dtype == MDS_F32C) f(DType<float, float, true>{});
+  else if (dtype == MDS_F32) f(DType<float, float>{});
+  else if (dtype == MDS_F64) f(DType<double, double>{});
+  else f(DType<float, half_t>{});
+}
+// with_dtype_no_half: the paths that are not built for fp16 storage (their entry points have refused MDS_F16 handles)
+template <typename F> static void with_dtype_no_half(int dtype, F&& f) {
+  if (dtype == MDS_F64) f(DType<double, double>{});
+  else if (dtype == MDS_F32C) f(DType<float, float, true>{});
+  else f(DType<float, float>{});
+}
 
 static inline dim3 grid_for(int n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 static inline bool is_comp(const mds_handle* h) { return h->cfg.dtype == MDS_F32C; }
-static inline bool is_f32(const mds_handle* h) { return h->cfg.dtype == MDS_F32 || h->cfg.dtype == MDS_F32C; }   // fp32 buffers
-template <typename T> static void fill_cbf(const mds_handle* h, const mds_cbf_params& p, CbfParams<T>& o) { fill_cbf_params(h->cfg, p, o); }
+// the handle's Consts in both compute types (set-up path: after a change to cfg, the gains or the wind)
+static void refill_consts(mds_handle* h) {
+  fill_consts(h->cfg, h->gains, h->p32.c, h->wind);
+  fill_consts(h->cfg, h->gains, h->p64.c, h->wind);
+}
 
 template <typename T> static void fill_lin_model(const double* A, const double* B, double u_eq0, LinModel<T>& M) {
   for (int r = 0; r < 12; ++r) {
@@ -314,10 +345,10 @@ static void launch_linear_xdot(const Consts<T>& C, int count, const void* x, con
 }
 
 // set-up path: (re)write one gain struct to its device copy, synchronously
-static int upload_gain(mds_handle* h, int slot, const void* f32, size_t nf, const void* f64, size_t nd) {
-  if (!h->gain_dev[slot]) MDS_HIP(hipMalloc(&h->gain_dev[slot], nd));
-  if (h->cfg.dtype == MDS_F64) MDS_HIP(hipMemcpy(h->gain_dev[slot], f64, nd, hipMemcpyHostToDevice));
-  else MDS_HIP(hipMemcpy(h->gain_dev[slot], f32, nf, hipMemcpyHostToDevice));
+template <typename GF, typename GD> static int upload_gain(mds_handle* h, int slot, const GF& f32, const GD& f64) {
+  if (!h->gain_dev[slot]) MDS_HIP(hipMalloc(&h->gain_dev[slot], sizeof(f64)));
+  if (h->cfg.dtype == MDS_F64) MDS_HIP(hipMemcpy(h->gain_dev[slot], &f64, sizeof(f64), hipMemcpyHostToDevice));
+  else MDS_HIP(hipMemcpy(h->gain_dev[slot], &f32, sizeof(f32), hipMemcpyHostToDevice));
   return MDS_OK;
 }
 
@@ -409,34 +440,12 @@ int mds_create(const mds_config* cfg, mds_handle** out) {
   mds_default_geometric_gains(&h->gains);
   h->n = cfg->num_envs * cfg->num_drones;
   h->ld = ((size_t)h->n + 255) / 256 * 256;
-  h->has_traj = false;
-  h->traj_mode = 0;
-  h->segs = nullptr;
-  h->tinfo = nullptr;
-  h->wind[0] = h->wind[1] = h->wind[2] = 0.0;
-  fill_consts(h->cfg, h->gains, h->cf, h->wind);
-  fill_consts(h->cfg, h->gains, h->cd, h->wind);
+  refill_consts(h);
   const size_t es = elem_size(cfg->dtype), cs = comp_size(cfg->dtype);
-  h->state = h->origin = h->last_rpm = h->lem = nullptr;
-  h->scratch = nullptr;
-  h->has_cbf = false;
-  h->pair_ij = nullptr;
-  h->obstacles = nullptr;
-  h->cbf_unom = h->cbf_xdes = h->cbf_usafe = h->ll = nullptr;
-  h->cbf_order = h->cbf_count = h->cbf_cost = nullptr;
-  h->cbf_calls = -1;
-  h->has_lqr = false;
-  h->has_lqr_yo = false;
-  h->has_lqr12 = false;
-  h->gain_dev[0] = h->gain_dev[1] = h->gain_dev[2] = nullptr;
-  h->cbf_nominal = 0;
-  h->pid = nullptr;
   h->envfx = cfg->physics >= MDS_PHYSICS_DYN_GND;
-  h->state_alt = nullptr;
-  fill_envfx(h->cfg, h->fx_f);
-  fill_envfx(h->cfg, h->fx_d);
+  fill_envfx(h->cfg, h->p32.fx);
+  fill_envfx(h->cfg, h->p64.fx);
   h->track_rpm = cfg->track_last_rpm != 0 || cfg->physics == MDS_PHYSICS_DYN_DRAG || cfg->physics == MDS_PHYSICS_DYN_GND_DRAG_DW;
-  h->rpm_stale = false;
   {
     mds_dslpid_gains dg;
     mds_default_dslpid_gains(&dg);
@@ -468,8 +477,12 @@ int mds_create(const mds_config* cfg, mds_handle** out) {
   {
     const size_t nbytes = (size_t)h->n * 6 * sizeof(double);
     MDS_HIP(hipMemset(h->scratch, 0, nbytes));
-    MDS_DISPATCH(h, (k_reset<T, S><<<grid_for(h->n, 256), 256, 0, 0>>>(h->n, h->ld, h->scratch, h->scratch + (size_t)3 * h->n,
-                                                                         (const T*)h->origin, (S*)h->state, (T*)h->last_rpm, 0, (S*)h->state_lo)));
+    with_dtype(h->cfg.dtype, [&](auto DT) {
+      using T = typename decltype(DT)::T;
+      using S = typename decltype(DT)::S;
+      k_reset<T, S><<<grid_for(h->n, 256), 256, 0, 0>>>(h->n, h->ld, h->scratch, h->scratch + (size_t)3 * h->n, (const T*)h->origin, (S*)h->state,
+                                                         (T*)h->last_rpm, 0, (S*)h->state_lo);
+    });
     MDS_HIP(hipGetLastError());
     MDS_HIP(hipDeviceSynchronize());
   }
@@ -541,8 +554,11 @@ int mds_get_derived(const mds_handle* h, double out[8]) {
 static int launch_reset_range(mds_handle* h, hipStream_t st, size_t i0, size_t i1) {
   const double* xyz = h->init_pose;
   const double* rpy = h->init_pose + (size_t)3 * h->n;
-  MDS_DISPATCH(h, (k_reset<T, S><<<grid_for(i1 - i0, 256), 256, 0, st>>>((int)i1, h->ld, xyz, rpy, (const T*)h->origin, (S*)h->state,
-                                                                          (T*)h->last_rpm, (int)i0, (S*)h->state_lo)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_reset<T, S><<<grid_for(i1 - i0, 256), 256, 0, st>>>((int)i1, h->ld, xyz, rpy, (const T*)h->origin, (S*)h->state, (T*)h->last_rpm, (int)i0,
+                                                           (S*)h->state_lo);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -592,8 +608,10 @@ int mds_get_state(mds_handle* h, double* out, void* stream) {
   MDS_DEV(h);
   if (!h || !out) return fail(MDS_EINVAL, "mds_get_state: null argument");
   hipStream_t st = (hipStream_t)stream;
-  MDS_DISPATCH(h, (k_get_state<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, (const S*)h->state, (const T*)h->origin,
-                                                                            h->scratch, (const S*)h->state_lo)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_get_state<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, (const S*)h->state, (const T*)h->origin, h->scratch, (const S*)h->state_lo);
+  });
   MDS_HIP(hipGetLastError());
   MDS_HIP(hipMemcpyAsync(out, h->scratch, (size_t)h->n * 13 * sizeof(double), hipMemcpyDeviceToHost, st));
   MDS_HIP(hipStreamSynchronize(st));
@@ -605,8 +623,10 @@ int mds_set_state(mds_handle* h, const double* in, void* stream) {
   if (!h || !in) return fail(MDS_EINVAL, "mds_set_state: null argument");
   hipStream_t st = (hipStream_t)stream;
   MDS_HIP(hipMemcpyAsync(h->scratch, in, (size_t)h->n * 13 * sizeof(double), hipMemcpyHostToDevice, st));
-  MDS_DISPATCH(h, (k_set_state<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, h->scratch, (const T*)h->origin,
-                                                                            (S*)h->state, (S*)h->state_lo)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_set_state<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, h->scratch, (const T*)h->origin, (S*)h->state, (S*)h->state_lo);
+  });
   MDS_HIP(hipGetLastError());
   MDS_HIP(hipStreamSynchronize(st));
   return MDS_OK;
@@ -617,7 +637,10 @@ int mds_set_origin(mds_handle* h, const double* origin, void* stream) {
   if (!h || !origin) return fail(MDS_EINVAL, "mds_set_origin: null argument");
   hipStream_t st = (hipStream_t)stream;
   MDS_HIP(hipMemcpyAsync(h->scratch, origin, (size_t)h->n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-  MDS_DISPATCH(h, (k_set_origin<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, h->scratch, (T*)h->origin, (S*)h->state, (S*)h->state_lo)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_set_origin<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, h->scratch, (T*)h->origin, (S*)h->state, (S*)h->state_lo);
+  });
   MDS_HIP(hipGetLastError());
   MDS_HIP(hipStreamSynchronize(st));
   return MDS_OK;
@@ -628,42 +651,35 @@ int mds_get_obs(mds_handle* h, void* obs, void* stream) {
   if (!h || !obs) return fail(MDS_EINVAL, "mds_get_obs: null argument");
   if (!aligned16(obs)) return fail(MDS_EALIGN, "mds_get_obs: obs_dev");
   hipStream_t st = (hipStream_t)stream;
-  MDS_DISPATCH(h, (k_get_obs<T, S><<<grid_for(h->n, kBlock), kBlock, 0, st>>>(h->n, h->ld, (const S*)h->state, (const T*)h->origin,
-                                                                                (const T*)(h->rpm_stale ? nullptr : h->last_rpm), (S*)obs)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_get_obs<T, S><<<grid_for(h->n, kBlock), kBlock, 0, st>>>(h->n, h->ld, (const S*)h->state, (const T*)h->origin,
+                                                                (const T*)(h->rpm_stale ? nullptr : h->last_rpm), (S*)obs);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
+}
+
+// Unused dynamic LDS of a half-shard launch in a two-chain rollout (launch_step_geometric says why).  stages_rows: the kernel has its
+// static LDS block for the observation rows (or the segment tables), else only its 16-byte minimum.
+static size_t split_lds_pad(const mds_handle* h, bool stages_rows) {
+  const size_t static_lds = stages_rows ? (size_t)kBlock * kObsDim * elem_size(h->cfg.dtype) : 16;
+  return static_lds < kSplitLds ? kSplitLds - static_lds : 0;
 }
 
 // k_step over 256-drone batches [batch0, batch0 + nb) (nb == 0: the whole shard); half-shard launches of a two-stream rollout
 // are padded to 32 KB LDS like the fused step's (launch_step_geometric)
 static void launch_step_plain(mds_handle* h, const void* action, void* obs, hipStream_t st, unsigned batch0 = 0, unsigned nb = 0) {
   const dim3 grid(nb ? nb : (unsigned)((h->n + kBlock - 1) / kBlock));
-  size_t pad = 0;
-  if (nb) {
-    const size_t static_lds = obs ? (size_t)kBlock * kObsDim * elem_size(h->cfg.dtype) : 16;
-    pad = static_lds < kSplitLds ? kSplitLds - static_lds : 0;
-  }
-#define MDS_LAUNCH_STEP(HAS_OBS, RK4, DRAG)                                                                          \
-  do {                                                                                                               \
-    if (is_comp(h))                                                                                                  \
-      k_step<float, float, HAS_OBS, RK4, DRAG, true><<<grid, kBlock, pad, st>>>(h->cf, h->n, h->ld, (float*)h->state, (const float*)h->origin, \
-                                                                                (float*)rpm_track(h), (const float*)action, (float*)obs, (int)batch0, (float*)h->state_lo); \
-    else                                                                                                             \
-      MDS_DISPATCH(h, (k_step<T, S, HAS_OBS, RK4, DRAG><<<grid, kBlock, pad, st>>>(C, h->n, h->ld, (S*)h->state, (const T*)h->origin, \
-                                                                                   (T*)rpm_track(h), (const S*)action, (S*)obs, (int)batch0))); \
-  } while (0)
-  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-#define MDS_STEP_OBS(HAS_OBS)                           \
-  do {                                                  \
-    if (rk4 && drag) MDS_LAUNCH_STEP(HAS_OBS, true, true);   \
-    else if (rk4) MDS_LAUNCH_STEP(HAS_OBS, true, false);     \
-    else if (drag) MDS_LAUNCH_STEP(HAS_OBS, false, true);    \
-    else MDS_LAUNCH_STEP(HAS_OBS, false, false);             \
-  } while (0)
-  if (obs) MDS_STEP_OBS(true);
-  else MDS_STEP_OBS(false);
-#undef MDS_STEP_OBS
-#undef MDS_LAUNCH_STEP
+  const size_t pad = nb ? split_lds_pad(h, obs != nullptr) : 0;
+  with_flags([&](auto HAS_OBS, auto RK4, auto DRAG) {
+    with_dtype(h->cfg.dtype, [&](auto DT) {
+      using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+      k_step<T, S, HAS_OBS(), RK4(), DRAG(), DT.COMP><<<grid, kBlock, pad, st>>>(params<T>(h).c, h->n, h->ld, (S*)h->state, (const T*)h->origin,
+                                                                                  (T*)rpm_track(h), (const S*)action, (S*)obs, (int)batch0,
+                                                                                  (S*)h->state_lo);
+    });
+  }, obs != nullptr, h->cfg.integrator == MDS_INTEGRATOR_RK4, has_drag(h));
 }
 
 // [UPSTREAM] BaseAviary.step under ground effect / downwash: one launch per physics substep on the double-buffered state
@@ -692,13 +708,13 @@ int step_env_plain(mds_handle* h, const void* action, void* obs, hipStream_t st,
   if (!home) home = h->state;
   for (int k = first_substep; k < K; ++k) {
     void* ob = k == K - 1 ? obs : nullptr;
-    if (h->cfg.dtype == MDS_F64) {
-      if (has_drag(h)) k_step_env<double, double, true><<<grid, kBlock, 0, st>>>(h->cd, h->fx_d, h->n, h->ld, D, (const double*)h->state, (double*)h->state_alt, (const double*)h->origin, (double*)rpm, (const double*)action, (double*)ob, k > 0, k == K - 1);
-      else k_step_env<double, double, false><<<grid, kBlock, 0, st>>>(h->cd, h->fx_d, h->n, h->ld, D, (const double*)h->state, (double*)h->state_alt, (const double*)h->origin, (double*)rpm, (const double*)action, (double*)ob, k > 0, k == K - 1);
-    } else {
-      if (has_drag(h)) k_step_env<float, float, true><<<grid, kBlock, 0, st>>>(h->cf, h->fx_f, h->n, h->ld, D, (const float*)h->state, (float*)h->state_alt, (const float*)h->origin, (float*)rpm, (const float*)action, (float*)ob, k > 0, k == K - 1);
-      else k_step_env<float, float, false><<<grid, kBlock, 0, st>>>(h->cf, h->fx_f, h->n, h->ld, D, (const float*)h->state, (float*)h->state_alt, (const float*)h->origin, (float*)rpm, (const float*)action, (float*)ob, k > 0, k == K - 1);
-    }
+    with_dtype_no_half(h->cfg.dtype, [&](auto DT) {        // ground effect / downwash: f32 / f64 storage only (mds_create)
+      using T = typename decltype(DT)::T;
+      with_flags([&](auto DRAG) {
+        k_step_env<T, T, DRAG()><<<grid, kBlock, 0, st>>>(params<T>(h).c, params<T>(h).fx, h->n, h->ld, D, (const T*)h->state, (T*)h->state_alt,
+                                                          (const T*)h->origin, (T*)rpm, (const T*)action, (T*)ob, k > 0, k == K - 1);
+      }, has_drag(h));
+    });
     void* t = h->state; h->state = h->state_alt; h->state_alt = t;
   }
   MDS_HIP(hipGetLastError());
@@ -714,29 +730,17 @@ int step_env_ctrl(mds_handle* h, int ctrl, double t, const void* u_in, double th
   void* rpm = rpm_track(h);
   void* abuf = K > 1 ? h->act_scratch : nullptr;
   const void* gain = ctrl == 1 ? h->gain_dev[0] : nullptr;
-  const bool drag = has_drag(h);
-#define MDS_CE(T, CC, FX, DRAG, CTRL)                                                                                              \
-  k_step_ctrl_env<T, T, DRAG, CTRL><<<grid, kBlock, 0, st>>>(CC, FX, gain, h->n, h->ld, D, t, h->traj_mode, (const T*)h->state, (T*)h->state_alt, \
-                                                             (const T*)h->origin, (const T*)h->lem, SegTable{h->segs, h->nseg_total}, h->tinfo, \
-                                                             (T*)rpm, (T*)h->ll, (const T*)u_in, (T)(1.0 / h->cfg.ctrl_freq), (T)thrust_offset,  \
-                                                             (T*)abuf, (T*)obs, (T*)act, K == 1)
-#define MDS_CE_D(T, CC, FX, CTRL)            \
-  do {                                       \
-    if (drag) MDS_CE(T, CC, FX, true, CTRL); \
-    else MDS_CE(T, CC, FX, false, CTRL);     \
-  } while (0)
-#define MDS_CE_C(T, CC, FX)                   \
-  do {                                        \
-    if (ctrl == 0) MDS_CE_D(T, CC, FX, 0);    \
-    else if (ctrl == 1) MDS_CE_D(T, CC, FX, 1); \
-    else if (ctrl == 2) MDS_CE_D(T, CC, FX, 2); \
-    else MDS_CE_D(T, CC, FX, 3);              \
-  } while (0)
-  if (h->cfg.dtype == MDS_F64) MDS_CE_C(double, h->cd, h->fx_d);
-  else MDS_CE_C(float, h->cf, h->fx_f);
-#undef MDS_CE_C
-#undef MDS_CE_D
-#undef MDS_CE
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {          // ground effect / downwash: f32 / f64 storage only (mds_create)
+    using T = typename decltype(DT)::T;
+    with_int<0, 1, 2, 3>(ctrl, [&](auto CTRL) {
+      with_flags([&](auto DRAG) {
+        k_step_ctrl_env<T, T, DRAG(), CTRL()><<<grid, kBlock, 0, st>>>(params<T>(h).c, params<T>(h).fx, gain, h->n, h->ld, D, t, h->traj_mode,
+                                                                       (const T*)h->state, (T*)h->state_alt, (const T*)h->origin, (const T*)h->lem,
+                                                                       SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm, (T*)h->ll, (const T*)u_in,
+                                                                       (T)(1.0 / h->cfg.ctrl_freq), (T)thrust_offset, (T*)abuf, (T*)obs, (T*)act, K == 1);
+      }, has_drag(h));
+    });
+  });
   MDS_HIP(hipGetLastError());
   void* home = h->state;
   void* tmp = h->state; h->state = h->state_alt; h->state_alt = tmp;
@@ -749,7 +753,6 @@ int mds_step(mds_handle* h, const void* action, void* obs, void* stream) {
   if (!h || !action) return fail(MDS_EINVAL, "mds_step: null argument");
   if (!aligned16(action) || !aligned16(obs)) return fail(MDS_EALIGN, "mds_step: action_dev/obs_dev");
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid = grid_for(h->n, kBlock);
   if (h->envfx) return step_env_plain(h, action, obs, st, 0);
   launch_step_plain(h, action, obs, st);
   MDS_HIP(hipGetLastError());
@@ -770,7 +773,10 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   delete[] centres;
   if (rc != MDS_OK) return rc;
   MDS_HIP(hipMemcpyAsync(h->scratch, params, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-  MDS_DISPATCH(h, (k_set_planes<T><<<grid_for(n, 256), 256, 0, st>>>(n, h->ld, 7, h->scratch, (T*)h->lem)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T;
+    k_set_planes<T><<<grid_for(n, 256), 256, 0, st>>>(n, h->ld, 7, h->scratch, (T*)h->lem);
+  });
   MDS_HIP(hipGetLastError());
   MDS_HIP(hipStreamSynchronize(st));
   h->has_traj = true;
@@ -898,9 +904,10 @@ int mds_traj_eval(mds_handle* h, double t, void* des, void* stream) {
   if (h->traj_mode == 1) return mds_lemniscate_eval(h, t, des, stream);
   if (h->traj_mode != 2) return fail(MDS_ESTATE, "mds_traj_eval: no trajectories set");
   hipStream_t st = (hipStream_t)stream;
-  if (h->cfg.dtype == MDS_F64) k_traj_eval<double><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, t, SegTable{h->segs, h->nseg_total}, h->tinfo, (double*)des);
-  else if (is_f32(h)) k_traj_eval<float><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, t, SegTable{h->segs, h->nseg_total}, h->tinfo, (float*)des);
-  else k_traj_eval<half_t><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, t, SegTable{h->segs, h->nseg_total}, h->tinfo, (half_t*)des);
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using S = typename decltype(DT)::S;
+    k_traj_eval<S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, t, SegTable{h->segs, h->nseg_total}, h->tinfo, (S*)des);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -909,16 +916,14 @@ int mds_set_geometric_gains(mds_handle* h, const mds_geometric_gains* g) {
   if (!h || !g) return fail(MDS_EINVAL, "mds_set_geometric_gains: null argument");
   if (!(g->max_tilt_angle > 0) || !(g->max_tilt_angle < M_PI / 2)) return fail(MDS_EINVAL, "mds_set_geometric_gains: max_tilt_angle");
   h->gains = *g;
-  fill_consts(h->cfg, h->gains, h->cf, h->wind);
-  fill_consts(h->cfg, h->gains, h->cd, h->wind);
+  refill_consts(h);
   return MDS_OK;
 }
 
 int mds_set_wind(mds_handle* h, const double force_world[3]) {
   if (!h || !force_world) return fail(MDS_EINVAL, "mds_set_wind: null argument");
   for (int k = 0; k < 3; ++k) h->wind[k] = force_world[k];
-  fill_consts(h->cfg, h->gains, h->cf, h->wind);
-  fill_consts(h->cfg, h->gains, h->cd, h->wind);
+  refill_consts(h);
   return MDS_OK;
 }
 
@@ -929,55 +934,28 @@ static int launch_step_geometric(mds_handle* h, double t, void* obs, void* act, 
   // instead of 8.  A half then no longer fits the chip next to the other chain's half, so its workgroups enter as the other
   // chain's retire and the two chains interleave from the first step on (C3: 15.6 -> 15.0 us per step over 20 000 steps,
   // 16.5 -> 15.8 over 2000; on one stream the same padding costs 4 %, so full-shard launches do not get it).
-  size_t pad = 0;
-  if (nb) {
-    const size_t static_lds = (h->traj_mode == 2 || obs) ? (size_t)kBlock * kObsDim * elem_size(h->cfg.dtype) : 16;
-    pad = static_lds < kSplitLds ? kSplitLds - static_lds : 0;
-  }
+  const size_t pad = nb ? split_lds_pad(h, h->traj_mode == 2 || obs) : 0;
+  const dim3 grid(nbatch);
+  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
   if (h->traj_mode == 2) {      // general trajectories: segment tables
-    const bool rk4_ = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag_ = has_drag(h);
-#define MDS_TRAJ(RK4, DRAG)                                                                                                   \
-  do {                                                                                                                        \
-    if (is_comp(h))                                                                                                           \
-      k_step_traj<float, float, RK4, DRAG, true><<<dim3(nbatch), kBlock, pad, st>>>(h->cf, h->n, h->ld, t, (float*)h->state, (const float*)h->origin, \
-                                                                                    SegTable{h->segs, h->nseg_total}, h->tinfo, (float*)rpm_track(h), (float*)obs, (float*)act, (int)batch0, (float*)h->state_lo); \
-    else                                                                                                                      \
-      MDS_DISPATCH(h, (k_step_traj<T, S, RK4, DRAG><<<dim3(nbatch), kBlock, pad, st>>>(C, h->n, h->ld, t, (S*)h->state, (const T*)h->origin, \
-                                                                                   SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm_track(h), (S*)obs, (S*)act, (int)batch0))); \
-  } while (0)
-    if (rk4_ && drag_) MDS_TRAJ(true, true);
-    else if (rk4_) MDS_TRAJ(true, false);
-    else if (drag_) MDS_TRAJ(false, true);
-    else MDS_TRAJ(false, false);
-#undef MDS_TRAJ
+    with_flags([&](auto RK4, auto DRAG) {
+      with_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+        k_step_traj<T, S, RK4(), DRAG(), DT.COMP><<<grid, kBlock, pad, st>>>(params<T>(h).c, h->n, h->ld, t, (S*)h->state, (const T*)h->origin,
+                                                                             SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm_track(h), (S*)obs,
+                                                                             (S*)act, (int)batch0, (S*)h->state_lo);
+      });
+    }, rk4, drag);
     return MDS_OK;
   }
-#define MDS_LAUNCH_GEO2(HAS_OBS, HAS_ACT, RK4, DRAG)                                                                           \
-  do {                                                                                                                         \
-    if (is_comp(h))                                                                                                            \
-      k_step_geometric<float, float, HAS_OBS, HAS_ACT, RK4, DRAG, true><<<grid, kBlock, pad, st>>>(h->cf, h->n, h->ld, t, (float*)h->state, \
-                                                                                                   (const float*)h->lem, (float*)rpm_track(h), \
-                                                                                                   (float*)obs, (float*)act, (int)batch0, (float*)h->state_lo); \
-    else                                                                                                                       \
-      MDS_DISPATCH(h, (k_step_geometric<T, S, HAS_OBS, HAS_ACT, RK4, DRAG><<<grid, kBlock, pad, st>>>(C, h->n, h->ld, t, (S*)h->state, \
-                                                                                                    (const T*)h->lem, (T*)rpm_track(h), \
-                                                                                                    (S*)obs, (S*)act, (int)batch0))); \
-  } while (0)
-  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-  const dim3 grid(nbatch);
-#define MDS_LAUNCH_GEO(HAS_OBS, HAS_ACT)                         \
-  do {                                                           \
-    if (rk4 && drag) MDS_LAUNCH_GEO2(HAS_OBS, HAS_ACT, true, true);   \
-    else if (rk4) MDS_LAUNCH_GEO2(HAS_OBS, HAS_ACT, true, false);     \
-    else if (drag) MDS_LAUNCH_GEO2(HAS_OBS, HAS_ACT, false, true);    \
-    else MDS_LAUNCH_GEO2(HAS_OBS, HAS_ACT, false, false);             \
-  } while (0)
-  if (obs && act) MDS_LAUNCH_GEO(true, true);
-  else if (obs) MDS_LAUNCH_GEO(true, false);
-  else if (act) MDS_LAUNCH_GEO(false, true);
-  else MDS_LAUNCH_GEO(false, false);
-#undef MDS_LAUNCH_GEO2
-#undef MDS_LAUNCH_GEO
+  with_flags([&](auto HAS_OBS, auto HAS_ACT, auto RK4, auto DRAG) {
+    with_dtype(h->cfg.dtype, [&](auto DT) {
+      using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+      k_step_geometric<T, S, HAS_OBS(), HAS_ACT(), RK4(), DRAG(), DT.COMP><<<grid, kBlock, pad, st>>>(params<T>(h).c, h->n, h->ld, t, (S*)h->state,
+                                                                                                      (const T*)h->lem, (T*)rpm_track(h), (S*)obs,
+                                                                                                      (S*)act, (int)batch0, (S*)h->state_lo);
+    });
+  }, obs != nullptr, act != nullptr, rk4, drag);
   return MDS_OK;
 }
 
@@ -992,83 +970,46 @@ int mds_step_geometric(mds_handle* h, double t, void* obs, void* act, void* stre
   return MDS_OK;
 }
 
-extern "C++" {
-// The kernels take the compensated storage (COMP: MDS_F32C handles) and the destination of the rows (OBS) as template arguments.  The
-// fp32-arithmetic Euler / no-drag GeometricControl loops (the bench's headline among them) are instantiated per destination; the other
-// combinations (RK4, drag, the LQR family, float64) take it at run time (OBS -1), as before: their register budget is set by the
-// arithmetic, not by the three expansions of the row writer, and the library would otherwise carry three copies of each.
-template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP>
-static void launch_rollout_variant(mds_handle* h, const Consts<T>& C, const void* gain, double t0, double dt, int n_steps, void* obs_log, size_t log_stride,
-                                   void* obs_last, dim3 grid, hipStream_t st) {
-  constexpr bool kPerObs = sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0;
-  const int omode = obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog;
-#define MDS_ROLL(OBS)                                                                                                                         \
-  do {                                                                                                                                        \
-    if (h->traj_mode == 2) {   /* general trajectories: segment tables */                                                                     \
-      if constexpr (CTRL <= 1)                                                                                                                \
-        k_rollout_traj<T, S, RK4, DRAG, CTRL, COMP, OBS><<<grid, kBlock, 0, st>>>(C, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->origin, \
-                                                                                  SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm_track(h), (S*)obs_log, \
-                                                                                  log_stride, (S*)obs_last, (S*)h->state_lo);                  \
-    } else {                                                                                                                                  \
-      k_rollout_geometric<T, S, RK4, DRAG, CTRL, COMP, OBS><<<grid, kBlock, 0, st>>>(C, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, \
-                                                                                     (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last, (T*)h->ll, \
-                                                                                     (const S*)obs_last, (S*)h->state_lo);                      \
-    }                                                                                                                                         \
-  } while (0)
-  if constexpr (kPerObs) {
-    if (omode == kObsInPlace) MDS_ROLL(kObsInPlace);
-    else if (omode == kObsLog) MDS_ROLL(kObsLog);
-    else MDS_ROLL(kObsLast);
-  } else {
-    MDS_ROLL(-1);
-  }
-#undef MDS_ROLL
-}
-
 // One launch of the whole-rollout kernel: n_steps control steps with the state in registers.  ctrl: 0 GeometricControl, 1 LQRController
 // (12-state), 2 LQROmegaController + ThrustOmega, 3 LQRYankOmegaController + YankOmega (Lemniscate trajectories only, no fp16 storage:
 // rollout_fused has refused the rest).  Step k's observation goes to obs_log + k * log_stride
 // elements (log_stride = n * 20: a [n_steps, n, 20] log; 0: every step overwrites the same [n, 20] buffer, what a step-by-step loop with one
 // observation buffer does); obs_last (or NULL) receives the last step's.
-template <typename T, typename S, int CTRL>
-static void launch_rollout_ctrl(mds_handle* h, const Consts<T>& C, double t0, int n_steps, void* obs_log, size_t log_stride, void* obs_last, hipStream_t st) {
+static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_steps, void* obs_log, size_t log_stride, void* obs_last, hipStream_t st) {
   const dim3 grid = grid_for(h->n, kBlock);
   const double dt = 1.0 / h->cfg.ctrl_freq;
-  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-  // the gain (up to 48 values) is read from its device copy: passing it by value would not fit beside Consts in SGPRs
-  const void* gain = CTRL >= 1 ? h->gain_dev[CTRL - 1] : nullptr;
-#define MDS_ROLL_P(RK4, DRAG)                                                                                                                  \
-  do {                                                                                                                                         \
-    if constexpr (std::is_same_v<S, float>) {                                                                                                  \
-      if (is_comp(h)) {                                                                                                                        \
-        launch_rollout_variant<T, S, RK4, DRAG, CTRL, 1>(h, C, gain, t0, dt, n_steps, obs_log, log_stride, obs_last, grid, st);                \
-        break;                                                                                                                                 \
-      }                                                                                                                                        \
-    }                                                                                                                                          \
-    launch_rollout_variant<T, S, RK4, DRAG, CTRL, 0>(h, C, gain, t0, dt, n_steps, obs_log, log_stride, obs_last, grid, st);                    \
-  } while (0)
-  if (rk4 && drag) MDS_ROLL_P(true, true);
-  else if (rk4) MDS_ROLL_P(true, false);
-  else if (drag) MDS_ROLL_P(false, true);
-  else MDS_ROLL_P(false, false);
-#undef MDS_ROLL_P
-}
-
-}  // extern "C++"
-
-static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_steps, void* obs_log, size_t log_stride, void* obs_last, hipStream_t st) {
-#define MDS_ROLL_C(CTRL) MDS_DISPATCH(h, (launch_rollout_ctrl<T, S, CTRL>(h, C, t0, n_steps, obs_log, log_stride, obs_last, st)))
-  if (ctrl == 3 || ctrl == 2) {
-    if (h->cfg.dtype == MDS_F64) {
-      if (ctrl == 3) launch_rollout_ctrl<double, double, 3>(h, h->cd, t0, n_steps, obs_log, log_stride, obs_last, st);
-      else launch_rollout_ctrl<double, double, 2>(h, h->cd, t0, n_steps, obs_log, log_stride, obs_last, st);
-    } else {
-      if (ctrl == 3) launch_rollout_ctrl<float, float, 3>(h, h->cf, t0, n_steps, obs_log, log_stride, obs_last, st);
-      else launch_rollout_ctrl<float, float, 2>(h, h->cf, t0, n_steps, obs_log, log_stride, obs_last, st);
-    }
-  } else if (ctrl == 1) MDS_ROLL_C(1);
-  else MDS_ROLL_C(0);
-#undef MDS_ROLL_C
+  const int omode = obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog;
+  auto launch = [&](auto DT, auto CTRL) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    constexpr int COMP = DT.COMP ? 1 : 0;
+    // the gain (up to 48 values) is read from its device copy: passing it by value would not fit beside Consts in SGPRs
+    const void* gain = nullptr;
+    if constexpr (CTRL() >= 1) gain = h->gain_dev[CTRL() - 1];
+    with_flags([&](auto RK4, auto DRAG) {
+      auto roll = [&](auto OBS) {
+        if (h->traj_mode == 2) {   // general trajectories: segment tables
+          if constexpr (CTRL() <= 1)
+            k_rollout_traj<T, S, RK4(), DRAG(), CTRL(), COMP, OBS()><<<grid, kBlock, 0, st>>>(
+                params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->origin, SegTable{h->segs, h->nseg_total}, h->tinfo,
+                (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last, (S*)h->state_lo);
+        } else {
+          k_rollout_geometric<T, S, RK4(), DRAG(), CTRL(), COMP, OBS()><<<grid, kBlock, 0, st>>>(
+              params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs_log, log_stride,
+              (S*)obs_last, (T*)h->ll, (const S*)obs_last, (S*)h->state_lo);
+        }
+      };
+      // The kernels take the compensated storage (COMP: MDS_F32C handles) and the destination of the rows (OBS) as template arguments.  The
+      // fp32-arithmetic Euler / no-drag GeometricControl loops (the bench's headline among them) are instantiated per destination; the other
+      // combinations (RK4, drag, the LQR family, float64) take it at run time (OBS -1), as before: their register budget is set by the
+      // arithmetic, not by the three expansions of the row writer, and the library would otherwise carry three copies of each.
+      constexpr bool kPerObs = sizeof(T) == 4 && !RK4() && !DRAG() && CTRL() == 0;
+      if constexpr (kPerObs) with_int<kObsInPlace, kObsLog, kObsLast>(omode, roll);
+      else roll(std::integral_constant<int, -1>{});
+    }, h->cfg.integrator == MDS_INTEGRATOR_RK4, has_drag(h));
+  };
+  // the LQR-omega / LQR-yank-omega loops are built for f32 / f32c / f64 only; GeometricControl and the 12-state LQR also for fp16 storage
+  if (ctrl >= 2) with_int<2, 3>(ctrl, [&](auto CTRL) { with_dtype_no_half(h->cfg.dtype, [&](auto DT) { launch(DT, CTRL); }); });
+  else with_int<1, 0>(ctrl, [&](auto CTRL) { with_dtype(h->cfg.dtype, [&](auto DT) { launch(DT, CTRL); }); });
 }
 
 int mds_rollout_geometric(mds_handle* h, double t0, int n_steps, void* obs, int obs_every_step, void* stream) {
@@ -1216,16 +1157,14 @@ int mds_rollout_step_fused(mds_handle* h, const void* actions, int n_action_sets
       if (chunk > to_boundary) chunk = to_boundary;
     }
     const int a0 = (int)(j % n_action_sets), s0 = obs_log ? (int)(j % log_slots) : 0;
-#define MDS_RS(RK4, DRAG)                                                                                                     \
-  MDS_DISPATCH(h, (k_rollout_step<T, S, RK4, DRAG><<<grid, kBlock, 0, st>>>(C, h->n, h->ld, (S*)h->state, (const T*)h->origin,  \
-                                                                            (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, \
-                                                                            (S*)obs_log, s0, obs_log ? log_slots : 1, (int)chunk, \
-                                                                            (S*)h->state_lo)))
-    if (rk4 && drag) MDS_RS(true, true);
-    else if (rk4) MDS_RS(true, false);
-    else if (drag) MDS_RS(false, true);
-    else MDS_RS(false, false);
-#undef MDS_RS
+    with_flags([&](auto RK4, auto DRAG) {
+      with_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+        k_rollout_step<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(params<T>(h).c, h->n, h->ld, (S*)h->state, (const T*)h->origin, (T*)rpm_track(h),
+                                                                     (const S*)actions, a0, n_action_sets, (S*)obs_log, s0, obs_log ? log_slots : 1,
+                                                                     (int)chunk, (S*)h->state_lo);
+      });
+    }, rk4, drag);
     j += chunk;
   }
   MDS_HIP(hipGetLastError());
@@ -1333,7 +1272,10 @@ int mds_lemniscate_eval(mds_handle* h, double t, void* des, void* stream) {
   MDS_DEV(h);
   if (!h || !des) return fail(MDS_EINVAL, "mds_lemniscate_eval: null argument");
   if (!h->has_traj || h->traj_mode != 1) return fail(MDS_ESTATE, "mds_lemniscate_eval: call mds_set_lemniscate first");
-  MDS_DISPATCH(h, (k_lemniscate_eval<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(h->n, h->ld, t, (const T*)h->lem, (S*)des)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_lemniscate_eval<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(h->n, h->ld, t, (const T*)h->lem, (S*)des);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1342,8 +1284,10 @@ int mds_geometric_compute(mds_handle* h, const void* obs, const void* des, void*
   MDS_DEV(h);
   if (!h || !obs || !des || !rpm) return fail(MDS_EINVAL, "mds_geometric_compute: null argument");
   if (!aligned16(rpm)) return fail(MDS_EALIGN, "mds_geometric_compute: rpm_dev");
-  MDS_DISPATCH(h, (k_geometric_compute<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(C, h->n, (const S*)obs, (const S*)des,
-                                                                                                     (S*)rpm, (S*)aux)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_geometric_compute<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(params<T>(h).c, h->n, (const S*)obs, (const S*)des, (S*)rpm, (S*)aux);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1352,7 +1296,10 @@ int mds_input_to_action(mds_handle* h, const void* u, void* rpm, void* stream) {
   MDS_DEV(h);
   if (!h || !u || !rpm) return fail(MDS_EINVAL, "mds_input_to_action: null argument");
   if (!aligned16(u) || !aligned16(rpm)) return fail(MDS_EALIGN, "mds_input_to_action");
-  MDS_DISPATCH(h, (k_input_to_action<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(C, h->n, (const S*)u, (S*)rpm)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_input_to_action<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(params<T>(h).c, h->n, (const S*)u, (S*)rpm);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1361,7 +1308,10 @@ int mds_obs_to_model(mds_handle* h, const void* obs, int dim, void* x, void* str
   MDS_DEV(h);
   if (!h || !obs || !x) return fail(MDS_EINVAL, "mds_obs_to_model: null argument");
   if (dim != 9 && dim != 10 && dim != 12 && dim != 18) return fail(MDS_EINVAL, "mds_obs_to_model: dim must be 9, 10, 12 (linear models) or 18 (geometric model)");
-  MDS_DISPATCH(h, (k_obs_to_model<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(C, h->n, dim, (const S*)obs, (S*)x)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_obs_to_model<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(params<T>(h).c, h->n, dim, (const S*)obs, (S*)x);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1370,7 +1320,10 @@ int mds_action_to_input(mds_handle* h, const void* rpm, int cap_rpm, void* u, vo
   MDS_DEV(h);
   if (!h || !u || !rpm) return fail(MDS_EINVAL, "mds_action_to_input: null argument");
   if (!aligned16(u) || !aligned16(rpm)) return fail(MDS_EALIGN, "mds_action_to_input");
-  MDS_DISPATCH(h, (k_action_to_input<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(C, h->n, cap_rpm, (const S*)rpm, (S*)u)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_action_to_input<T, S><<<grid_for(h->n, 256), 256, 0, (hipStream_t)stream>>>(params<T>(h).c, h->n, cap_rpm, (const S*)rpm, (S*)u);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1379,19 +1332,12 @@ int mds_quadrotor_dynamics(int dtype, int count, const void* state, const void* 
                            void* out, void* stream) {
   if (count < 0 || !state || !u || !out || !J) return fail(MDS_EINVAL, "mds_quadrotor_dynamics: bad argument");
   if (count == 0) return MDS_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid = grid_for(count, 256);
-  if (dtype == MDS_F32)
-    k_quadrotor_dynamics<float, float><<<grid, 256, 0, st>>>(count, (const float*)state, (const float*)u, (float)m, (float)J[0],
-                                                              (float)J[1], (float)J[2], (float)g, (float*)out);
-  else if (dtype == MDS_F64)
-    k_quadrotor_dynamics<double, double><<<grid, 256, 0, st>>>(count, (const double*)state, (const double*)u, m, J[0], J[1], J[2], g,
-                                                                (double*)out);
-  else if (dtype == MDS_F16)
-    k_quadrotor_dynamics<float, half_t><<<grid, 256, 0, st>>>(count, (const half_t*)state, (const half_t*)u, (float)m, (float)J[0],
-                                                               (float)J[1], (float)J[2], (float)g, (half_t*)out);
-  else
-    return fail(MDS_EINVAL, "mds_quadrotor_dynamics: dtype");
+  if (dtype != MDS_F32 && dtype != MDS_F64 && dtype != MDS_F16) return fail(MDS_EINVAL, "mds_quadrotor_dynamics: dtype");
+  with_dtype(dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_quadrotor_dynamics<T, S><<<grid_for(count, 256), 256, 0, (hipStream_t)stream>>>(count, (const S*)state, (const S*)u, (T)m, (T)J[0], (T)J[1],
+                                                                                       (T)J[2], (T)g, (S*)out);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1403,7 +1349,10 @@ int mds_compare_models(mds_handle* h, int count, const void* obs, const double* 
   if (!xdot_lin && !xdot_geo && !x_lin) return fail(MDS_EINVAL, "mds_compare_models: no output requested");
   if (!aligned16(obs) || !aligned16(xdot_lin) || !aligned16(xdot_geo) || !aligned16(x_lin)) return fail(MDS_EALIGN, "mds_compare_models");
   if (count == 0) return MDS_OK;
-  MDS_DISPATCH(h, (launch_compare_models<T, S>(C, count, obs, A, B, u_eq0, dyn_m, dyn_J, dyn_g, xdot_lin, xdot_geo, x_lin, (hipStream_t)stream)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    launch_compare_models<T, S>(params<T>(h).c, count, obs, A, B, u_eq0, dyn_m, dyn_J, dyn_g, xdot_lin, xdot_geo, x_lin, (hipStream_t)stream);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1413,7 +1362,10 @@ int mds_linear_xdot(mds_handle* h, int count, const void* x, const void* action,
   MDS_DEV(h);
   if (!h || count < 0 || !x || !action || !A || !B || !xdot) return fail(MDS_EINVAL, "mds_linear_xdot: bad argument");
   if (count == 0) return MDS_OK;
-  MDS_DISPATCH(h, (launch_linear_xdot<T, S>(C, count, x, action, A, B, u_eq0, xdot, (hipStream_t)stream)));
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    launch_linear_xdot<T, S>(params<T>(h).c, count, x, action, A, B, u_eq0, xdot, (hipStream_t)stream);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1421,12 +1373,11 @@ int mds_linear_xdot(mds_handle* h, int count, const void* x, const void* action,
 int mds_rpy_to_rot(int dtype, int count, const void* rpy, void* R, void* stream) {
   if (count < 0 || !rpy || !R) return fail(MDS_EINVAL, "mds_rpy_to_rot: bad argument");
   if (count == 0) return MDS_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid = grid_for(count, 256);
-  if (dtype == MDS_F32) k_rpy_to_rot<float, float><<<grid, 256, 0, st>>>(count, (const float*)rpy, (float*)R);
-  else if (dtype == MDS_F64) k_rpy_to_rot<double, double><<<grid, 256, 0, st>>>(count, (const double*)rpy, (double*)R);
-  else if (dtype == MDS_F16) k_rpy_to_rot<float, half_t><<<grid, 256, 0, st>>>(count, (const half_t*)rpy, (half_t*)R);
-  else return fail(MDS_EINVAL, "mds_rpy_to_rot: dtype");
+  if (dtype != MDS_F32 && dtype != MDS_F64 && dtype != MDS_F16) return fail(MDS_EINVAL, "mds_rpy_to_rot: dtype");
+  with_dtype(dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_rpy_to_rot<T, S><<<grid_for(count, 256), 256, 0, (hipStream_t)stream>>>(count, (const S*)rpy, (S*)R);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1434,12 +1385,11 @@ int mds_rpy_to_rot(int dtype, int count, const void* rpy, void* R, void* stream)
 int mds_geo_model_to_obs(int dtype, int count, const void* x18, void* obs16, void* stream) {
   if (count < 0 || !x18 || !obs16) return fail(MDS_EINVAL, "mds_geo_model_to_obs: bad argument");
   if (count == 0) return MDS_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid = grid_for(count, 256);
-  if (dtype == MDS_F32) k_geo_model_to_obs<float, float><<<grid, 256, 0, st>>>(count, (const float*)x18, (float*)obs16);
-  else if (dtype == MDS_F64) k_geo_model_to_obs<double, double><<<grid, 256, 0, st>>>(count, (const double*)x18, (double*)obs16);
-  else if (dtype == MDS_F16) k_geo_model_to_obs<float, half_t><<<grid, 256, 0, st>>>(count, (const half_t*)x18, (half_t*)obs16);
-  else return fail(MDS_EINVAL, "mds_geo_model_to_obs: dtype");
+  if (dtype != MDS_F32 && dtype != MDS_F64 && dtype != MDS_F16) return fail(MDS_EINVAL, "mds_geo_model_to_obs: dtype");
+  with_dtype(dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_geo_model_to_obs<T, S><<<grid_for(count, 256), 256, 0, (hipStream_t)stream>>>(count, (const S*)x18, (S*)obs16);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1492,8 +1442,8 @@ int mds_cbf_configure(mds_handle* h, const mds_cbf_params* p, const double* obst
     if (const char* fused = getenv("MDS_CBF_FUSED")) h->cbf_fused = fused[0] == '1';       // unset: what mds_cbf_set_step_kernel chose
   }
   h->cbf = *p;
-  fill_cbf(h, *p, h->cbf_f);
-  fill_cbf(h, *p, h->cbf_d);
+  fill_cbf_params(h->cfg, *p, h->p32.cbf);
+  fill_cbf_params(h->cfg, *p, h->p64.cbf);
   h->has_cbf = true;
   return MDS_OK;
 }
@@ -1509,16 +1459,12 @@ int mds_cbf_rows(mds_handle* h, const void* x, const void* xdes, void* G, void* 
   if (!h->has_cbf) return fail(MDS_ESTATE, "mds_cbf_rows: call mds_cbf_configure first");
   hipStream_t st = (hipStream_t)stream;
   const int E = h->cfg.num_envs;
-#define MDS_ROWS(T, CP, ORD)                                                                                            \
-  k_cbf_rows<T, T, ORD><<<E, 256, 0, st>>>(CP, E, h->pair_ij, (const T*)h->obstacles, (const T*)x, (const T*)xdes, (T*)G, (T*)hv)
-  if (h->cfg.dtype == MDS_F64) {
-    if (h->cbf.order == 2) MDS_ROWS(double, h->cbf_d, 2);
-    else MDS_ROWS(double, h->cbf_d, 3);
-  } else {
-    if (h->cbf.order == 2) MDS_ROWS(float, h->cbf_f, 2);
-    else MDS_ROWS(float, h->cbf_f, 3);
-  }
-#undef MDS_ROWS
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {          // the ECBF filter: f32 / f32c / f64 (mds_cbf_configure refuses fp16 storage)
+    using T = typename decltype(DT)::T;
+    with_int<2, 3>(h->cbf.order, [&](auto ORD) {
+      k_cbf_rows<T, T, ORD()><<<E, 256, 0, st>>>(params<T>(h).cbf, E, h->pair_ij, (const T*)h->obstacles, (const T*)x, (const T*)xdes, (T*)G, (T*)hv);
+    });
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1555,66 +1501,37 @@ static int cbf_filter_range(mds_handle* h, const void* obs_, const void* xdes_, 
   const int* ord_in = calls < 0 ? nullptr : order_tab;
   const int* cnt_in = calls < 0 ? nullptr : count_tab;
   int* cost_out = hildreth ? nullptr : cost_tab;
-  // one wavefront (= one env) per workgroup; NMAX bounds the QP variables (LDS footprint of Q, R ~ NMAX^2)
-#define MDS_GI(T, CP, RR, NMAX, ORD, TOL)                                                                                   \
-  k_cbf_filter_gi<T, T, RR, NMAX, ORD><<<dim3((unsigned)E), 64, 0, st>>>(                                                    \
-      CP, E, (T)h->cfg.KF, h->pair_ij, (const T*)h->obstacles, (const T*)obs, (const T*)xdes, (const T*)unom, (T*)usafe,     \
-      (int*)status, max_iter, (T)((TOL) * (TOL)), ord_in, cnt_in, cost_out)
-#define MDS_GI_R(T, CP, NMAX, ORD, TOL)            \
-  do {                                             \
-    if (R <= 4) MDS_GI(T, CP, 4, NMAX, ORD, TOL);  \
-    else if (R <= 8) MDS_GI(T, CP, 8, NMAX, ORD, TOL); \
-    else MDS_GI(T, CP, 17, NMAX, ORD, TOL);        \
-  } while (0)
-#define MDS_GI_ALL(T, CP, TOL)                                       \
-  do {                                                               \
-    if (order == 2) {                                                \
-      if (n <= 16) MDS_GI_R(T, CP, 16, 2, TOL);                      \
-      else MDS_GI_R(T, CP, 32, 2, TOL);                              \
-    } else {                                                         \
-      if (n <= 24) MDS_GI_R(T, CP, 24, 3, TOL);                      \
-      else if (n <= 48) MDS_GI_R(T, CP, 48, 3, TOL);                 \
-      else MDS_GI_R(T, CP, 63, 3, TOL);                              \
-    }                                                                \
-  } while (0)
-#define MDS_HILD(T, CP, RR, TOL)                                                                                          \
-  k_cbf_filter_o2<T, T, RR><<<grid, 256, 0, st>>>(CP, E, h->pair_ij, (const T*)h->obstacles, (const T*)obs, (const T*)xdes, \
-                                                  (const T*)unom, (T*)usafe, (int*)status, max_iter, (T)((TOL) * (TOL)))
-#define MDS_HILD_R(T, CP, TOL)              \
-  do {                                      \
-    if (R <= 4) MDS_HILD(T, CP, 4, TOL);    \
-    else if (R <= 8) MDS_HILD(T, CP, 8, TOL); \
-    else MDS_HILD(T, CP, 17, TOL);          \
-  } while (0)
   // order 2 with at most 16 thrust variables and 224 rows: four envs per wavefront, one per 16-lane row (k_cbf_filter_q4)
   const bool q4 = h->cbf_q4 && !hildreth && order == 2 && n <= 16 && m <= 224;
-#define MDS_Q4(T, CP, RL, TOL)                                                                                                    \
-  k_cbf_filter_q4<T, T, RL><<<dim3((unsigned)((E + 3) / 4)), 64, 0, st>>>(CP, E, h->pair_ij, (const T*)h->obstacles, (const T*)obs, \
-                                                                          (const T*)xdes, (const T*)unom, (T*)usafe, (int*)status,  \
-                                                                          max_iter, (T)((TOL) * (TOL)), cost_out)
-#define MDS_Q4_R(T, CP, TOL)               \
-  do {                                     \
-    if (m <= 128) MDS_Q4(T, CP, 8, TOL);   \
-    else MDS_Q4(T, CP, 14, TOL);           \
-  } while (0)
-  if (h->cfg.dtype == MDS_F64) {
-    const double tol = h->cbf.tol > 0 ? h->cbf.tol : 1e-12;
-    if (q4) MDS_Q4_R(double, h->cbf_d, tol);
-    else if (hildreth) MDS_HILD_R(double, h->cbf_d, tol);
-    else MDS_GI_ALL(double, h->cbf_d, tol);
-  } else {
-    const double tol = h->cbf.tol > 0 ? h->cbf.tol : 1e-6;
-    if (q4) MDS_Q4_R(float, h->cbf_f, tol);
-    else if (hildreth) MDS_HILD_R(float, h->cbf_f, tol);
-    else MDS_GI_ALL(float, h->cbf_f, tol);
-  }
-#undef MDS_Q4_R
-#undef MDS_Q4
-#undef MDS_HILD_R
-#undef MDS_HILD
-#undef MDS_GI_ALL
-#undef MDS_GI_R
-#undef MDS_GI
+  const int RR = R <= 4 ? 4 : (R <= 8 ? 8 : 17);           // row registers per lane the kernels are built for
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {          // f32 / f32c / f64 (mds_cbf_configure refuses fp16 storage)
+    using T = typename decltype(DT)::T;
+    const CbfParams<T>& P = params<T>(h).cbf;
+    const double tol = h->cbf.tol > 0 ? h->cbf.tol : (sizeof(T) == 8 ? 1e-12 : 1e-6);
+    const T tol2 = (T)(tol * tol);
+    if (q4) {
+      with_int<8, 14>(m <= 128 ? 8 : 14, [&](auto RL) {
+        k_cbf_filter_q4<T, T, RL()><<<grid, 64, 0, st>>>(P, E, h->pair_ij, (const T*)h->obstacles, (const T*)obs, (const T*)xdes, (const T*)unom,
+                                                         (T*)usafe, (int*)status, max_iter, tol2, cost_out);
+      });
+    } else if (hildreth) {
+      with_int<4, 8, 17>(RR, [&](auto R_) {
+        k_cbf_filter_o2<T, T, R_()><<<grid, 256, 0, st>>>(P, E, h->pair_ij, (const T*)h->obstacles, (const T*)obs, (const T*)xdes, (const T*)unom,
+                                                          (T*)usafe, (int*)status, max_iter, tol2);
+      });
+    } else {
+      // one wavefront (= one env) per workgroup; NMAX bounds the QP variables (LDS footprint of Q, R ~ NMAX^2)
+      auto gi = [&](auto ORD, auto NMAX) {
+        with_int<4, 8, 17>(RR, [&](auto R_) {
+          k_cbf_filter_gi<T, T, R_(), NMAX(), ORD()><<<dim3((unsigned)E), 64, 0, st>>>(P, E, (T)h->cfg.KF, h->pair_ij, (const T*)h->obstacles,
+                                                                                      (const T*)obs, (const T*)xdes, (const T*)unom, (T*)usafe,
+                                                                                      (int*)status, max_iter, tol2, ord_in, cnt_in, cost_out);
+        });
+      };
+      if (order == 2) with_int<16, 32>(n <= 16 ? 16 : 32, [&](auto NMAX) { gi(std::integral_constant<int, 2>{}, NMAX); });
+      else with_int<24, 48, 63>(n <= 24 ? 24 : (n <= 48 ? 48 : 63), [&](auto NMAX) { gi(std::integral_constant<int, 3>{}, NMAX); });
+    }
+  });
   MDS_HIP(hipGetLastError());
   if (!hildreth && !q4 && E >= 1024) {                    // small batches have no tail to hide
     if (calls < 0 || calls >= 7) {
@@ -1658,10 +1575,12 @@ int mds_default_dslpid_gains(mds_dslpid_gains* g) {
 int mds_set_dslpid_gains(mds_handle* h, const mds_dslpid_gains* g) {
   if (!h || !g) return fail(MDS_EINVAL, "mds_set_dslpid_gains: null argument");
   for (int k = 0; k < 3; ++k) {
-    h->pid_d.Pf[k] = g->P_COEFF_FOR[k]; h->pid_d.If[k] = g->I_COEFF_FOR[k]; h->pid_d.Df[k] = g->D_COEFF_FOR[k];
-    h->pid_d.Pt[k] = g->P_COEFF_TOR[k]; h->pid_d.It[k] = g->I_COEFF_TOR[k]; h->pid_d.Dt[k] = g->D_COEFF_TOR[k];
-    h->pid_f.Pf[k] = (float)g->P_COEFF_FOR[k]; h->pid_f.If[k] = (float)g->I_COEFF_FOR[k]; h->pid_f.Df[k] = (float)g->D_COEFF_FOR[k];
-    h->pid_f.Pt[k] = (float)g->P_COEFF_TOR[k]; h->pid_f.It[k] = (float)g->I_COEFF_TOR[k]; h->pid_f.Dt[k] = (float)g->D_COEFF_TOR[k];
+    DslPidGains<double>& d = h->p64.pid;
+    DslPidGains<float>& f = h->p32.pid;
+    d.Pf[k] = g->P_COEFF_FOR[k]; d.If[k] = g->I_COEFF_FOR[k]; d.Df[k] = g->D_COEFF_FOR[k];
+    d.Pt[k] = g->P_COEFF_TOR[k]; d.It[k] = g->I_COEFF_TOR[k]; d.Dt[k] = g->D_COEFF_TOR[k];
+    f.Pf[k] = (float)g->P_COEFF_FOR[k]; f.If[k] = (float)g->I_COEFF_FOR[k]; f.Df[k] = (float)g->D_COEFF_FOR[k];
+    f.Pt[k] = (float)g->P_COEFF_TOR[k]; f.It[k] = (float)g->I_COEFF_TOR[k]; f.Dt[k] = (float)g->D_COEFF_TOR[k];
   }
   return MDS_OK;
 }
@@ -1673,43 +1592,34 @@ int mds_dslpid_reset(mds_handle* h, void* stream) {
   return MDS_OK;
 }
 
-// PID_GRID / PID_B0: the launch's batches (all of them, or one half of the shard in a two-chain rollout)
-#define MDS_PID_LAUNCH(T, S, C, G, STEP, RK4, DRAG)                                                                           \
-  k_dslpid<T, S, STEP, RK4, DRAG><<<PID_GRID, kBlock, 0, st>>>(C, G, h->n, h->ld, (T)(1.0 / h->cfg.ctrl_freq), (S*)h->state, \
-                                                               (const T*)h->origin, (T*)rpm_track(h), (T*)h->pid,            \
-                                                               (const S*)obs_in, (const S*)tpos, (const S*)trpy, (S*)obs,   \
-                                                               (S*)act, PID_B0, (S*)h->state_lo)
-#define MDS_PID_DTYPE(STEP, RK4, DRAG)                                                        \
-  do {                                                                                        \
-    if (h->cfg.dtype == MDS_F64) MDS_PID_LAUNCH(double, double, h->cd, h->pid_d, STEP, RK4, DRAG); \
-    else if (is_f32(h)) MDS_PID_LAUNCH(float, float, h->cf, h->pid_f, STEP, RK4, DRAG); \
-    else MDS_PID_LAUNCH(float, half_t, h->cf, h->pid_f, STEP, RK4, DRAG);                     \
-  } while (0)
+// k_dslpid over the batches [batch0, batch0 + nb) (nb == 0: the whole shard).  step: the controller and the physics step of one
+// MultiDroneEnv.sim_step (reads the handle's state; obs_in unused); else the controller alone on obs_in (or the handle's state), action to act.
+static void launch_dslpid(mds_handle* h, bool step, const void* obs_in, const void* tpos, const void* trpy, void* obs, void* act, hipStream_t st,
+                          unsigned batch0 = 0, unsigned nb = 0) {
+  const dim3 grid = nb ? dim3(nb) : grid_for(h->n, kBlock);
+  auto launch = [&](auto STEP, auto RK4, auto DRAG) {
+    with_dtype(h->cfg.dtype, [&](auto DT) {
+      using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+      k_dslpid<T, S, STEP(), RK4(), DRAG()><<<grid, kBlock, 0, st>>>(params<T>(h).c, params<T>(h).pid, h->n, h->ld, (T)(1.0 / h->cfg.ctrl_freq),
+                                                                   (S*)h->state, (const T*)h->origin, (T*)rpm_track(h), (T*)h->pid, (const S*)obs_in,
+                                                                   (const S*)tpos, (const S*)trpy, (S*)obs, (S*)act, (int)batch0, (S*)h->state_lo);
+    });
+  };
+  if (step) with_flags([&](auto RK4, auto DRAG) { launch(std::true_type{}, RK4, DRAG); }, h->cfg.integrator == MDS_INTEGRATOR_RK4, has_drag(h));
+  else launch(std::false_type{}, std::false_type{}, std::false_type{});         // the controller alone integrates nothing: one instantiation
+}
 
 // one MultiDroneEnv.sim_step for the batches [batch0, batch0 + nb) (nb == 0: the whole shard)
 static void launch_step_dslpid(mds_handle* h, const void* tpos, const void* trpy, void* obs, void* act, hipStream_t st, unsigned batch0 = 0,
                                unsigned nb = 0) {
-  const dim3 PID_GRID = nb ? dim3(nb) : grid_for(h->n, kBlock);
-  const int PID_B0 = (int)batch0;
-  const void* obs_in = nullptr;
-  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-  if (rk4 && drag) MDS_PID_DTYPE(true, true, true);
-  else if (rk4) MDS_PID_DTYPE(true, true, false);
-  else if (drag) MDS_PID_DTYPE(true, false, true);
-  else MDS_PID_DTYPE(true, false, false);
+  launch_dslpid(h, true, nullptr, tpos, trpy, obs, act, st, batch0, nb);
 }
 
 // the same step under ground effect / downwash: the controller reads the handle's state and leaves the action in act_scratch (or the
 // caller's buffer), then env.step runs it one substep per launch
 static int step_env_dslpid(mds_handle* h, const void* tpos, const void* trpy, void* obs, void* act_out, hipStream_t st) {
-  const dim3 PID_GRID = grid_for(h->n, kBlock);
-  const int PID_B0 = 0;
-  const void* obs_in = nullptr;
   void* act = act_out ? act_out : h->act_scratch;
-  {
-    void* obs = nullptr;
-    MDS_PID_DTYPE(false, false, false);
-  }
+  launch_dslpid(h, false, nullptr, tpos, trpy, nullptr, act, st);
   return step_env_plain(h, act, obs, st, 0);
 }
 
@@ -1717,11 +1627,7 @@ int mds_dslpid_compute(mds_handle* h, const void* obs_in, const void* tpos, cons
   MDS_DEV(h);
   if (!h || !obs_in || !tpos || !trpy || !act) return fail(MDS_EINVAL, "mds_dslpid_compute: null argument");
   if (!aligned16(act)) return fail(MDS_EALIGN, "mds_dslpid_compute: rpm_dev");
-  hipStream_t st = (hipStream_t)stream;
-  void* obs = nullptr;
-  const dim3 PID_GRID = grid_for(h->n, kBlock);
-  const int PID_B0 = 0;
-  MDS_PID_DTYPE(false, false, false);
+  launch_dslpid(h, false, obs_in, tpos, trpy, nullptr, act, (hipStream_t)stream);
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1784,19 +1690,17 @@ int mds_rollout_dslpid(mds_handle* h, const void* tpos, const void* trpy, int n_
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
-#undef MDS_PID_DTYPE
-#undef MDS_PID_LAUNCH
 
 int mds_set_lqr_omega_gain(mds_handle* h, const double K[36]) {
   MDS_DEV(h);
   if (!h || !K) return fail(MDS_EINVAL, "mds_set_lqr_omega_gain: null argument");
   for (int r = 0; r < 4; ++r)
     for (int k = 0; k < 9; ++k) {
-      h->lqr_d.k[r][k] = K[9 * r + k];
-      h->lqr_f.k[r][k] = (float)K[9 * r + k];
+      h->p64.lqr.k[r][k] = K[9 * r + k];
+      h->p32.lqr.k[r][k] = (float)K[9 * r + k];
     }
   h->has_lqr = true;
-  return upload_gain(h, 1, &h->lqr_f, sizeof(h->lqr_f), &h->lqr_d, sizeof(h->lqr_d));
+  return upload_gain(h, 1, h->p32.lqr, h->p64.lqr);
 }
 
 int mds_lqr_omega_compute(mds_handle* h, const void* obs, const void* des, void* u, void* stream) {
@@ -1805,12 +1709,10 @@ int mds_lqr_omega_compute(mds_handle* h, const void* obs, const void* des, void*
   if (!h->has_lqr) return fail(MDS_ESTATE, "mds_lqr_omega_compute: call mds_set_lqr_omega_gain first");
   if (!aligned16(u)) return fail(MDS_EALIGN, "mds_lqr_omega_compute: u_dev");
   hipStream_t st = (hipStream_t)stream;
-  if (h->cfg.dtype == MDS_F64)
-    k_lqr_omega_compute<double, double><<<grid_for(h->n, 256), 256, 0, st>>>(h->cd, h->lqr_d, h->n, (const double*)obs, (const double*)des, (double*)u);
-  else if (is_f32(h))
-    k_lqr_omega_compute<float, float><<<grid_for(h->n, 256), 256, 0, st>>>(h->cf, h->lqr_f, h->n, (const float*)obs, (const float*)des, (float*)u);
-  else
-    k_lqr_omega_compute<float, half_t><<<grid_for(h->n, 256), 256, 0, st>>>(h->cf, h->lqr_f, h->n, (const half_t*)obs, (const half_t*)des, (half_t*)u);
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_lqr_omega_compute<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(params<T>(h).c, params<T>(h).lqr, h->n, (const S*)obs, (const S*)des, (S*)u);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1820,11 +1722,11 @@ int mds_set_lqr_gain(mds_handle* h, const double K[48]) {
   if (!h || !K) return fail(MDS_EINVAL, "mds_set_lqr_gain: null argument");
   for (int r = 0; r < 4; ++r)
     for (int k = 0; k < 12; ++k) {
-      h->lqr12_d.k[r][k] = K[12 * r + k];
-      h->lqr12_f.k[r][k] = (float)K[12 * r + k];
+      h->p64.lqr12.k[r][k] = K[12 * r + k];
+      h->p32.lqr12.k[r][k] = (float)K[12 * r + k];
     }
   h->has_lqr12 = true;
-  return upload_gain(h, 0, &h->lqr12_f, sizeof(h->lqr12_f), &h->lqr12_d, sizeof(h->lqr12_d));
+  return upload_gain(h, 0, h->p32.lqr12, h->p64.lqr12);
 }
 
 int mds_lqr_compute(mds_handle* h, const void* obs, const void* des, void* u, void* action, void* stream) {
@@ -1833,12 +1735,11 @@ int mds_lqr_compute(mds_handle* h, const void* obs, const void* des, void* u, vo
   if (!h->has_lqr12) return fail(MDS_ESTATE, "mds_lqr_compute: call mds_set_lqr_gain first");
   if (!aligned16(u) || !aligned16(action)) return fail(MDS_EALIGN, "mds_lqr_compute: u_dev/action_dev");
   hipStream_t st = (hipStream_t)stream;
-  if (h->cfg.dtype == MDS_F64)
-    k_lqr12_compute<double, double><<<grid_for(h->n, 256), 256, 0, st>>>(h->cd, h->lqr12_d, h->n, (const double*)obs, (const double*)des, (double*)u, (double*)action);
-  else if (is_f32(h))
-    k_lqr12_compute<float, float><<<grid_for(h->n, 256), 256, 0, st>>>(h->cf, h->lqr12_f, h->n, (const float*)obs, (const float*)des, (float*)u, (float*)action);
-  else
-    k_lqr12_compute<float, half_t><<<grid_for(h->n, 256), 256, 0, st>>>(h->cf, h->lqr12_f, h->n, (const half_t*)obs, (const half_t*)des, (half_t*)u, (half_t*)action);
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_lqr12_compute<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(params<T>(h).c, params<T>(h).lqr12, h->n, (const S*)obs, (const S*)des, (S*)u,
+                                                                (S*)action);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1853,22 +1754,14 @@ int mds_step_lqr(mds_handle* h, double t, void* obs, void* act, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid = grid_for(h->n, kBlock);
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-#define MDS_LQR_T(T, S, C, K, RK4, DRAG)                                                                                          \
-  k_step_lqr<T, S, RK4, DRAG><<<grid, kBlock, 0, st>>>(C, K, h->n, h->ld, t, h->traj_mode, (S*)h->state, (const T*)h->origin,     \
-                                                       (const T*)h->lem, SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm_track(h), (S*)obs, (S*)act, \
-                                                       (S*)h->state_lo)
-#define MDS_LQR(RK4, DRAG)                                                                    \
-  do {                                                                                        \
-    if (h->cfg.dtype == MDS_F64) MDS_LQR_T(double, double, h->cd, h->lqr12_d, RK4, DRAG);     \
-    else if (is_f32(h)) MDS_LQR_T(float, float, h->cf, h->lqr12_f, RK4, DRAG);  \
-    else MDS_LQR_T(float, half_t, h->cf, h->lqr12_f, RK4, DRAG);                              \
-  } while (0)
-  if (rk4 && drag) MDS_LQR(true, true);
-  else if (rk4) MDS_LQR(true, false);
-  else if (drag) MDS_LQR(false, true);
-  else MDS_LQR(false, false);
-#undef MDS_LQR
-#undef MDS_LQR_T
+  with_flags([&](auto RK4, auto DRAG) {
+    with_dtype(h->cfg.dtype, [&](auto DT) {
+      using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+      k_step_lqr<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(params<T>(h).c, params<T>(h).lqr12, h->n, h->ld, t, h->traj_mode, (S*)h->state,
+                                                               (const T*)h->origin, (const T*)h->lem, SegTable{h->segs, h->nseg_total}, h->tinfo,
+                                                               (T*)rpm_track(h), (S*)obs, (S*)act, (S*)h->state_lo);
+    });
+  }, rk4, drag);
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1878,11 +1771,11 @@ int mds_set_lqr_yank_omega_gain(mds_handle* h, const double K[40]) {
   if (!h || !K) return fail(MDS_EINVAL, "mds_set_lqr_yank_omega_gain: null argument");
   for (int r = 0; r < 4; ++r)
     for (int k = 0; k < 10; ++k) {
-      h->lqr_yo_d.k[r][k] = K[10 * r + k];
-      h->lqr_yo_f.k[r][k] = (float)K[10 * r + k];
+      h->p64.lqr_yo.k[r][k] = K[10 * r + k];
+      h->p32.lqr_yo.k[r][k] = (float)K[10 * r + k];
     }
   h->has_lqr_yo = true;
-  return upload_gain(h, 2, &h->lqr_yo_f, sizeof(h->lqr_yo_f), &h->lqr_yo_d, sizeof(h->lqr_yo_d));
+  return upload_gain(h, 2, h->p32.lqr_yo, h->p64.lqr_yo);
 }
 
 int mds_lqr_yank_omega_compute(mds_handle* h, const void* obs, const void* des, void* u, void* stream) {
@@ -1891,12 +1784,11 @@ int mds_lqr_yank_omega_compute(mds_handle* h, const void* obs, const void* des, 
   if (!h->has_lqr_yo) return fail(MDS_ESTATE, "mds_lqr_yank_omega_compute: call mds_set_lqr_yank_omega_gain first");
   if (!aligned16(u)) return fail(MDS_EALIGN, "mds_lqr_yank_omega_compute: u_dev");
   hipStream_t st = (hipStream_t)stream;
-  if (h->cfg.dtype == MDS_F64)
-    k_lqr_yank_omega_compute<double, double><<<grid_for(h->n, 256), 256, 0, st>>>(h->cd, h->lqr_yo_d, h->n, (const double*)obs, (const double*)des, (double*)u);
-  else if (is_f32(h))
-    k_lqr_yank_omega_compute<float, float><<<grid_for(h->n, 256), 256, 0, st>>>(h->cf, h->lqr_yo_f, h->n, (const float*)obs, (const float*)des, (float*)u);
-  else
-    k_lqr_yank_omega_compute<float, half_t><<<grid_for(h->n, 256), 256, 0, st>>>(h->cf, h->lqr_yo_f, h->n, (const half_t*)obs, (const half_t*)des, (half_t*)u);
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_lqr_yank_omega_compute<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(params<T>(h).c, params<T>(h).lqr_yo, h->n, (const S*)obs, (const S*)des,
+                                                                         (S*)u);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -1929,10 +1821,12 @@ int mds_lowlevel_reset(mds_handle* h, void* stream) {
   return MDS_OK;
 }
 
-static int launch_thrust_omega(mds_handle* h, const void* u, const void* src, int rates_given, int yank, void* rpm, hipStream_t st) {
-  MDS_DISPATCH(h, (k_thrust_omega<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(C, h->n, h->ld, (T)(1.0 / h->cfg.ctrl_freq), rates_given, yank,
-                                                                             (T*)h->ll, (const S*)u, (const S*)src, (S*)rpm)));
-  return MDS_OK;
+static void launch_thrust_omega(mds_handle* h, const void* u, const void* src, int rates_given, int yank, void* rpm, hipStream_t st) {
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_thrust_omega<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(params<T>(h).c, h->n, h->ld, (T)(1.0 / h->cfg.ctrl_freq), rates_given, yank, (T*)h->ll,
+                                                               (const S*)u, (const S*)src, (S*)rpm);
+  });
 }
 
 int mds_yank_omega_compute(mds_handle* h, const void* u, const void* obs, void* rpm, void* stream) {
@@ -1989,26 +1883,18 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
       h->cbf_last_step_kernel = 1;
       const void* gain = h->cbf_nominal == 1 ? h->gain_dev[1] : nullptr;
       void* rpm = rpm_track(h);
-#define MDS_CS(T, CC, CP, RR, NOM, COMP, TOL)                                                                                                \
-  k_cbf_step<T, RR, NOM, COMP><<<grid64, 64, 0, st>>>(CC, CP, gain, (int)j1, h->ld, h->cfg.num_envs, t, (T)(1.0 / h->cfg.ctrl_freq), (T*)h->state, \
-                                                      (T*)h->state_lo, (const T*)h->lem, (T*)rpm, (T*)h->ll, h->pair_ij, (const T*)h->obstacles,   \
-                                                      (T*)obs, (int*)status, h->cbf_cost, max_iter, (T)((TOL) * (TOL)), batch0)
-#define MDS_CS_N(T, CC, CP, RR, COMP, TOL)                         \
-  do {                                                             \
-    if (h->cbf_nominal == 1) MDS_CS(T, CC, CP, RR, 1, COMP, TOL);  \
-    else MDS_CS(T, CC, CP, RR, 0, COMP, TOL);                      \
-  } while (0)
-#define MDS_CS_R(T, CC, CP, COMP, TOL)                 \
-  do {                                                 \
-    if (m2 <= 256) MDS_CS_N(T, CC, CP, 4, COMP, TOL);  \
-    else MDS_CS_N(T, CC, CP, 8, COMP, TOL);            \
-  } while (0)
-      if (h->cfg.dtype == MDS_F64) MDS_CS_R(double, h->cd, h->cbf_d, false, (h->cbf.tol > 0 ? h->cbf.tol : 1e-12));
-      else if (is_comp(h)) MDS_CS_R(float, h->cf, h->cbf_f, true, (h->cbf.tol > 0 ? h->cbf.tol : 1e-6));
-      else MDS_CS_R(float, h->cf, h->cbf_f, false, (h->cbf.tol > 0 ? h->cbf.tol : 1e-6));
-#undef MDS_CS_R
-#undef MDS_CS_N
-#undef MDS_CS
+      with_dtype_no_half(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T;
+        const double tol = h->cbf.tol > 0 ? h->cbf.tol : (sizeof(T) == 8 ? 1e-12 : 1e-6);
+        with_int<4, 8>(m2 <= 256 ? 4 : 8, [&](auto RR) {
+          with_int<1, 0>(h->cbf_nominal, [&](auto NOM) {
+            k_cbf_step<T, RR(), NOM(), DT.COMP><<<grid64, 64, 0, st>>>(params<T>(h).c, params<T>(h).cbf, gain, (int)j1, h->ld, h->cfg.num_envs, t,
+                                                                       (T)(1.0 / h->cfg.ctrl_freq), (T*)h->state, (T*)h->state_lo, (const T*)h->lem,
+                                                                       (T*)rpm, (T*)h->ll, h->pair_ij, (const T*)h->obstacles, (T*)obs, (int*)status,
+                                                                       h->cbf_cost, max_iter, (T)(tol * tol), batch0);
+          });
+        });
+      });
       MDS_HIP(hipGetLastError());
       return MDS_OK;
     }
@@ -2032,43 +1918,28 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
   const void* nom_K = h->cbf_nominal == 1 ? h->gain_dev[1] : nullptr;
   // k_lowlevel_step: (a) `only` mode = the nominal controller of this step (GeometricControl / LQR-omega: the ONE compiled copy of
   // cbf_nominal_of, see there); (b) low level + physics + observation, optionally followed by the nominal input of the next step
-#define MDS_NX(T, S, ON, TT, ONLY) NextNominal<T, S>{(ON) ? (const T*)h->lem : nullptr, nom_K, (ON) ? (S*)h->cbf_unom : nullptr, (S*)h->cbf_xdes, TT, \
-                                                     (T)hover_sub, h->cbf_nominal, ONLY}
-#define MDS_LL(RK4, DRAG, YANK, ULL, OFFS, ON, TT, ONLY)                                                                         \
-  do {                                                                                                                           \
-    if (is_comp(h))                                                                                                              \
-      k_lowlevel_step<float, float, RK4, DRAG, YANK, true><<<grid, kBlock, 0, st>>>(h->cf, n_end, h->ld, (float)(1.0 / h->cfg.ctrl_freq), \
-                                                                                    (float)(OFFS), (float*)h->state, (const float*)h->origin, \
-                                                                                    (float*)rpm_track(h), (float*)h->ll, (const float*)(ULL), \
-                                                                                    (float*)obs, (float*)action, batch0, (float*)h->state_lo, \
-                                                                                    MDS_NX(float, float, ON, TT, ONLY));         \
-    else                                                                                                                         \
-      MDS_DISPATCH(h, (k_lowlevel_step<T, S, RK4, DRAG, YANK><<<grid, kBlock, 0, st>>>(C, n_end, h->ld, (T)(1.0 / h->cfg.ctrl_freq),  \
-                                                                                     (T)(OFFS), (S*)h->state, (const T*)h->origin, \
-                                                                                     (T*)rpm_track(h), (T*)h->ll, (const S*)(ULL), \
-                                                                                     (S*)obs, (S*)action, batch0, (S*)nullptr,    \
-                                                                                     MDS_NX(T, S, ON, TT, ONLY))));               \
-  } while (0)
-#define MDS_LL_Y(YANK, ULL, OFFS, ON, TT, ONLY)                         \
-  do {                                                                  \
-    if (rk4 && drag) MDS_LL(true, true, YANK, ULL, OFFS, ON, TT, ONLY); \
-    else if (rk4) MDS_LL(true, false, YANK, ULL, OFFS, ON, TT, ONLY);   \
-    else if (drag) MDS_LL(false, true, YANK, ULL, OFFS, ON, TT, ONLY);  \
-    else MDS_LL(false, false, YANK, ULL, OFFS, ON, TT, ONLY);           \
-  } while (0)
+  auto lowlevel = [&](bool yank_ll, const void* u_in, double offs, bool next_on, double t_nx, int only) {
+    with_flags([&](auto YANK, auto RK4, auto DRAG) {
+      with_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+        const NextNominal<T, S> nx{next_on ? (const T*)h->lem : nullptr, nom_K, next_on ? (S*)h->cbf_unom : nullptr, (S*)h->cbf_xdes, t_nx, (T)hover_sub,
+                                   h->cbf_nominal, only};
+        k_lowlevel_step<T, S, RK4(), DRAG(), YANK(), DT.COMP><<<grid, kBlock, 0, st>>>(params<T>(h).c, n_end, h->ld, (T)(1.0 / h->cfg.ctrl_freq), (T)offs,
+                                                                                      (S*)h->state, (const T*)h->origin, (T*)rpm_track(h), (T*)h->ll,
+                                                                                      (const S*)u_in, (S*)obs, (S*)action, batch0, (S*)h->state_lo, nx);
+      });
+    }, yank_ll, rk4, drag);
+  };
   if (skip_nominal) {
     // u_hat / xdes of this step came out of the previous step's low-level launch
   } else if (h->cbf_nominal == 2) {
-    if (h->cfg.dtype == MDS_F64)
-      k_cbf_nominal_lqr_yo<double, double><<<grid, kBlock, 0, st>>>(h->cd, h->lqr_yo_d, n_end, h->ld, t, hover_sub, (const double*)h->state,
-                                                                    (const double*)h->lem, (const double*)obs, (double*)h->cbf_unom,
-                                                                    (double*)h->cbf_xdes, batch0);
-    else
-      k_cbf_nominal_lqr_yo<float, float><<<grid, kBlock, 0, st>>>(h->cf, h->lqr_yo_f, n_end, h->ld, t, (float)hover_sub, (const float*)h->state,
-                                                                  (const float*)h->lem, (const float*)obs, (float*)h->cbf_unom,
-                                                                  (float*)h->cbf_xdes, batch0);
+    with_dtype_no_half(h->cfg.dtype, [&](auto DT) {       // the LQR family: f32 / f32c / f64 only (the entry points refuse fp16 storage)
+      using T = typename decltype(DT)::T;
+      k_cbf_nominal_lqr_yo<T, T><<<grid, kBlock, 0, st>>>(params<T>(h).c, params<T>(h).lqr_yo, n_end, h->ld, t, (T)hover_sub, (const T*)h->state,
+                                                          (const T*)h->lem, (const T*)obs, (T*)h->cbf_unom, (T*)h->cbf_xdes, batch0);
+    });
   } else {
-    MDS_LL_Y(false, nullptr, 0.0, true, t, 1);
+    lowlevel(false, nullptr, 0.0, true, t, 1);
   }
   MDS_HIP(hipGetLastError());
   const void* u_ll = h->cbf_unom;
@@ -2084,11 +1955,7 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
   const bool next_on = want_next && !yank && h->cbf_nominal <= 1 && !action;
   h->next_nom_ok[rg.slot] = next_on;
   h->next_nom_t[rg.slot] = t_next;
-  if (yank) MDS_LL_Y(true, u_ll, ll_offset, false, t_next, 0);
-  else MDS_LL_Y(false, u_ll, ll_offset, next_on, t_next, 0);
-#undef MDS_LL_Y
-#undef MDS_LL
-#undef MDS_NX
+  lowlevel(yank, u_ll, ll_offset, next_on, t_next, 0);
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -2202,21 +2069,18 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
     for (int k0 = 0; k0 < n_steps; k0 += steps_per_launch) {
       const int ks = n_steps - k0 < steps_per_launch ? n_steps - k0 : steps_per_launch;
       int32_t* slog = status_log ? status_log + (size_t)k0 * h->cfg.num_envs : nullptr;
-#define MDS_O3(T, CC, CP, KK, RR, NM, TOL)                                                                                                   \
-  k_cbf_rollout_o3<T, RR, NM><<<dim3((unsigned)h->cfg.num_envs), 64, 0, st3>>>(CC, CP, KK, h->cfg.num_envs, h->ld, t3, dt3, ks, (T*)h->state,   \
-                                                                             (const T*)h->lem, (T*)rpm3, (T*)h->ll, h->pair_ij,              \
-                                                                             (const T*)h->obstacles, (T*)obs, (T*)obs_log, slot3,            \
-                                                                             log_slots > 0 ? log_slots : 1, (int*)status, (int*)slog,        \
-                                                                             h->cbf_cost, max_iter3, (T)((TOL) * (TOL)), (T)hover_sub)
-#define MDS_O3_S(T, CC, CP, KK, TOL)                 \
-  do {                                               \
-    if (n3 <= 24 && m3 <= 256) MDS_O3(T, CC, CP, KK, 4, 24, TOL); \
-    else MDS_O3(T, CC, CP, KK, 8, 48, TOL);          \
-  } while (0)
-      if (h->cfg.dtype == MDS_F64) MDS_O3_S(double, h->cd, h->cbf_d, h->lqr_yo_d, (h->cbf.tol > 0 ? h->cbf.tol : 1e-12));
-      else MDS_O3_S(float, h->cf, h->cbf_f, h->lqr_yo_f, (h->cbf.tol > 0 ? h->cbf.tol : 1e-6));
-#undef MDS_O3_S
-#undef MDS_O3
+      with_dtype_no_half(h->cfg.dtype, [&](auto DT) {       // f32 / f64 (checked above)
+        using T = typename decltype(DT)::T;
+        const double tol = h->cbf.tol > 0 ? h->cbf.tol : (sizeof(T) == 8 ? 1e-12 : 1e-6);
+        auto launch = [&](auto RR, auto NM) {               // row registers per lane, bound on the QP variables
+          k_cbf_rollout_o3<T, RR(), NM()><<<dim3((unsigned)h->cfg.num_envs), 64, 0, st3>>>(
+              params<T>(h).c, params<T>(h).cbf, params<T>(h).lqr_yo, h->cfg.num_envs, h->ld, t3, dt3, ks, (T*)h->state, (const T*)h->lem, (T*)rpm3,
+              (T*)h->ll, h->pair_ij, (const T*)h->obstacles, (T*)obs, (T*)obs_log, slot3, log_slots > 0 ? log_slots : 1, (int*)status, (int*)slog,
+              h->cbf_cost, max_iter3, (T)(tol * tol), (T)hover_sub);
+        };
+        if (n3 <= 24 && m3 <= 256) launch(std::integral_constant<int, 4>{}, std::integral_constant<int, 24>{});
+        else launch(std::integral_constant<int, 8>{}, std::integral_constant<int, 48>{});
+      });
       MDS_HIP(hipGetLastError());
       for (int j = 0; j < ks; ++j) t3 += dt3;
       if (obs_log) slot3 = (slot3 + ks) % log_slots;
@@ -2257,27 +2121,21 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
   for (int k0 = 0; k0 < n_steps; k0 += steps_per_launch) {
     const int ks = n_steps - k0 < steps_per_launch ? n_steps - k0 : steps_per_launch;
     int32_t* slog = status_log ? status_log + (size_t)k0 * h->cfg.num_envs : nullptr;
-#define MDS_CR(T, CC, CP, NOM, COMP, TOL)                                                                                                        \
-  do {                                                                                                                                           \
-    RollArgs<T> ra;                                                                                                                              \
-    ra.p.c = CC; ra.p.P = CP; ra.Kp = gain; ra.n = (int)h->n; ra.ld = h->ld; ra.E = h->cfg.num_envs;             \
-    ra.t = t; ra.ctrl_dt = dt; ra.n_steps = ks; ra.state = (T*)h->state; ra.state_lo = (T*)h->state_lo; ra.lem = (const T*)h->lem;                \
-    ra.last_rpm = (T*)rpm; ra.ll = (T*)h->ll; ra.pair_ij = h->pair_ij; ra.obstacles = (const T*)h->obstacles; ra.obs_log = (T*)obs_log;           \
-    ra.slot = slot; ra.n_slots = log_slots > 0 ? log_slots : 1; ra.obs_last = (T*)obs; ra.status = (int*)status; ra.status_log = (int*)slog;      \
-    ra.cost_io = h->cbf_cost; ra.max_iter = max_iter; ra.tol2 = (T)((TOL) * (TOL)); ra.tol = (T)(TOL); ra.stamps = stamps_dev;                   \
-    if (D == Dp) k_cbf_rollout<T, NOM, COMP, (sizeof(T) == 8 ? NWD : NWF), false><<<grid, 64 * nw, 0, st>>>(ra);                                  \
-    else k_cbf_rollout<T, NOM, COMP, (sizeof(T) == 8 ? NWD : NWF), true><<<grid, 64 * nw, 0, st>>>(ra);                                           \
-  } while (0)
-#define MDS_CR_N(T, CC, CP, COMP, TOL)                        \
-  do {                                                        \
-    if (h->cbf_nominal == 1) MDS_CR(T, CC, CP, 1, COMP, TOL); \
-    else MDS_CR(T, CC, CP, 0, COMP, TOL);                     \
-  } while (0)
-    if (h->cfg.dtype == MDS_F64) MDS_CR_N(double, h->cd, h->cbf_d, false, (h->cbf.tol > 0 ? h->cbf.tol : 1e-12));
-    else if (is_comp(h)) MDS_CR_N(float, h->cf, h->cbf_f, true, (h->cbf.tol > 0 ? h->cbf.tol : 1e-6));
-    else MDS_CR_N(float, h->cf, h->cbf_f, false, (h->cbf.tol > 0 ? h->cbf.tol : 1e-6));
-#undef MDS_CR_N
-#undef MDS_CR
+    with_dtype_no_half(h->cfg.dtype, [&](auto DT) {         // f32 / f32c / f64 (roll_fused_applies)
+      using T = typename decltype(DT)::T;
+      const double tol = h->cbf.tol > 0 ? h->cbf.tol : (sizeof(T) == 8 ? 1e-12 : 1e-6);
+      RollArgs<T> ra;
+      ra.p.c = params<T>(h).c; ra.p.P = params<T>(h).cbf; ra.Kp = gain; ra.n = (int)h->n; ra.ld = h->ld; ra.E = h->cfg.num_envs;
+      ra.t = t; ra.ctrl_dt = dt; ra.n_steps = ks; ra.state = (T*)h->state; ra.state_lo = (T*)h->state_lo; ra.lem = (const T*)h->lem;
+      ra.last_rpm = (T*)rpm; ra.ll = (T*)h->ll; ra.pair_ij = h->pair_ij; ra.obstacles = (const T*)h->obstacles; ra.obs_log = (T*)obs_log;
+      ra.slot = slot; ra.n_slots = log_slots > 0 ? log_slots : 1; ra.obs_last = (T*)obs; ra.status = (int*)status; ra.status_log = (int*)slog;
+      ra.cost_io = h->cbf_cost; ra.max_iter = max_iter; ra.tol2 = (T)(tol * tol); ra.tol = (T)tol; ra.stamps = stamps_dev;
+      with_int<1, 0>(h->cbf_nominal, [&](auto NOM) {
+        with_flags([&](auto PAD) {                          // PAD: the env width D is not itself 4, 8 or 16 lanes
+          k_cbf_rollout<T, NOM(), DT.COMP, (sizeof(T) == 8 ? NWD : NWF), PAD()><<<grid, 64 * nw, 0, st>>>(ra);
+        }, D != Dp);
+      });
+    });
     MDS_HIP(hipGetLastError());
     // t advances on the host exactly as inside the kernel (one += per step), so that consecutive launches continue the same sequence
     for (int j = 0; j < ks; ++j) t += dt;
@@ -2433,19 +2291,14 @@ int mds_fedce_identify(mds_handle* h, int n_steps, const double* u_dev, int u_mo
   if (n_steps > 0) {
     const FedceModel fm = {h->cfg.M * h->cfg.G, h->cfg.G, h->cfg.M, {h->cfg.J[0], h->cfg.J[1], h->cfg.J[2]}, 1.0 / h->cfg.ctrl_freq};
     const dim3 grid = grid_for(h->n * 16, kFedceBlock);
-    const bool drag = has_drag(h);
-#define MDS_FEDCE_ID(T, C, DRAG)                                                                                                    \
-    k_fedce_identify<T, T, DRAG><<<grid, kFedceBlock, 0, st>>>(C, h->cd, fm, h->n, h->ld, n_steps, (T*)h->state, (const T*)h->origin,     \
-                                                               (T*)rpm_track(h), u_dev, u_mode, xdes_dev, update, h->fedce_P,          \
-                                                               h->fedce_theta, (T*)obs_log_dev, pred_err_log_dev, theta_log_dev)
-    if (h->cfg.dtype == MDS_F64) {
-      if (drag) MDS_FEDCE_ID(double, h->cd, true);
-      else MDS_FEDCE_ID(double, h->cd, false);
-    } else {
-      if (drag) MDS_FEDCE_ID(float, h->cf, true);
-      else MDS_FEDCE_ID(float, h->cf, false);
-    }
-#undef MDS_FEDCE_ID
+    with_dtype_no_half(h->cfg.dtype, [&](auto DT) {         // f32 / f64 (mds_fedce_supported)
+      using T = typename decltype(DT)::T;
+      with_flags([&](auto DRAG) {
+        k_fedce_identify<T, T, DRAG()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, h->p64.c, fm, h->n, h->ld, n_steps, (T*)h->state, (const T*)h->origin,
+                                                                     (T*)rpm_track(h), u_dev, u_mode, xdes_dev, update, h->fedce_P, h->fedce_theta,
+                                                                     (T*)obs_log_dev, pred_err_log_dev, theta_log_dev);
+      }, has_drag(h));
+    });
     MDS_HIP(hipGetLastError());
   }
   if (obs_dev) {
@@ -2491,12 +2344,11 @@ int mds_dlqr_compute(mds_handle* h, const void* obs, const void* des, void* u, v
   if (!aligned16(u) || !aligned16(action)) return fail(MDS_EALIGN, "mds_dlqr_compute: u_dev/action_dev");
   const int E = h->cfg.num_envs, D = h->cfg.num_drones, epb = kFedceBlock / D;
   const dim3 grid((unsigned)((E + epb - 1) / epb));
-  if (h->cfg.dtype == MDS_F64)
-    k_dlqr_compute<double, double><<<grid, kFedceBlock, 0, (hipStream_t)stream>>>(h->cd, (const double*)h->dlqr_K, E, D, (const double*)obs,
-                                                                                  (const double*)des, (double*)u, (double*)action);
-  else
-    k_dlqr_compute<float, float><<<grid, kFedceBlock, 0, (hipStream_t)stream>>>(h->cf, (const float*)h->dlqr_K, E, D, (const float*)obs,
-                                                                                (const float*)des, (float*)u, (float*)action);
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {           // f32 / f64 (mds_fedce_supported)
+    using T = typename decltype(DT)::T;
+    k_dlqr_compute<T, T><<<grid, kFedceBlock, 0, (hipStream_t)stream>>>(params<T>(h).c, (const T*)h->dlqr_K, E, D, (const T*)obs, (const T*)des, (T*)u,
+                                                                        (T*)action);
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
@@ -2513,19 +2365,14 @@ int mds_rollout_dlqr_fused(mds_handle* h, double t0, int n_steps, void* obs_log,
   const dim3 grid((unsigned)((E + epb - 1) / epb));
   const double dt = 1.0 / h->cfg.ctrl_freq;
   hipStream_t st = (hipStream_t)stream;
-#define MDS_DLQR(T, C, DRAG)                                                                                                         \
-  k_dlqr_rollout<T, T, DRAG><<<grid, kFedceBlock, 0, st>>>(C, (const T*)h->dlqr_K, E, D, h->ld, t0, dt, n_steps, h->traj_mode, (T*)h->state, \
-                                                           (const T*)h->origin, (const T*)h->lem, SegTable{h->segs, h->nseg_total},       \
-                                                           h->tinfo, (T*)rpm_track(h), (T*)obs_log, (T*)obs_last)
-  const bool drag = has_drag(h);
-  if (h->cfg.dtype == MDS_F64) {
-    if (drag) MDS_DLQR(double, h->cd, true);
-    else MDS_DLQR(double, h->cd, false);
-  } else {
-    if (drag) MDS_DLQR(float, h->cf, true);
-    else MDS_DLQR(float, h->cf, false);
-  }
-#undef MDS_DLQR
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {           // f32 / f64 (mds_fedce_supported)
+    using T = typename decltype(DT)::T;
+    with_flags([&](auto DRAG) {
+      k_dlqr_rollout<T, T, DRAG()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, (const T*)h->dlqr_K, E, D, h->ld, t0, dt, n_steps, h->traj_mode,
+                                                                 (T*)h->state, (const T*)h->origin, (const T*)h->lem, SegTable{h->segs, h->nseg_total},
+                                                                 h->tinfo, (T*)rpm_track(h), (T*)obs_log, (T*)obs_last);
+    }, has_drag(h));
+  });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
