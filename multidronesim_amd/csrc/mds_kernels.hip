@@ -511,13 +511,13 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
       for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
     {
       const Desired<T> des = lemniscate_local(P, t);
-      const M3<T> R = quat_to_rot(s.q);
-      const V3<T> ang_v = mul(R, s.w);
+      const Frame<T> F = make_frame(s.q, s.w);
       T u[4];
-      geometric_control<T>(c, s.p - des.p, R, s.v, ang_v, des, u, nullptr);
+      geometric_control<T>(c, s.p - des.p, F.R, s.v, F.av, des, u, nullptr);
       input_to_action(c, u, act);
+      if (COMP) aviary_step_comp<T, RK4, DRAG>(c, s, in.r, act, prev, clipped);
+      else aviary_step<T, RK4, DRAG>(c, s, F, act, prev, clipped);
     }
-    aviary_step_any<T, RK4, DRAG, COMP>(c, s, in.r, act, prev, clipped);
     if (DRAG || last_rpm)
       for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
     if (HAS_ACT) store4<S, T>(action_out + (size_t)i * 4, act);
@@ -726,6 +726,12 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
       if (CTRL == 3) load4<S, T>(obs_prev + (size_t)i * kObsDim + 16, thr);      // calc_z_thrust(obs) of the first step
     }
   }
+  // CTRL 0: the frame of the state is carried across the step loop -- the one formed for step k's observation row (the state after
+  // step k) is the one step k + 1's controller and rigid-body step read.  Where only the last step's rows leave (kObsLast) there is no
+  // row to share it with: the frame is formed at the top of the step, as in k_step_geometric (the same values either way).
+  constexpr bool kCarry = CTRL == 0 && OBS != kObsLast;
+  Frame<T> F;
+  if (kCarry && valid) F = make_frame(in.s.q, in.s.w);
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     const bool last = k == n_steps - 1;
@@ -751,9 +757,13 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
         const Desired<T> des = lemniscate_local(in.P, t);
         T u[4];
         if (CTRL == 0) {
-          const M3<T> R = quat_to_rot(in.s.q);
-          const V3<T> ang_v = mul(R, in.s.w);
-          geometric_control<T>(c, in.s.p - des.p, R, in.s.v, ang_v, des, u, nullptr);
+          if (!kCarry) {
+            F = make_frame(in.s.q, in.s.w);
+          } else if (kLean) {    // R22 is not carried beside R22 - 1: 1 + (-a) is the 1 - a of make_frame to the bit
+            MDS_KEEP_V(F.r22m1);
+            F.R.m[8] = T(1) + F.r22m1;
+          }
+          geometric_control<T>(c, in.s.p - des.p, F.R, in.s.v, F.av, des, u, nullptr);
         } else if (CTRL == 1) {
           lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(in.s.q), quat_rotate(in.s.q, in.s.w), in.s.v, in.s.p - des.p,
                            des.v, des.yaw, des.yaw_rate, u);
@@ -767,11 +777,18 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
         else if (CTRL == 2) thrust_omega_control(c, (T)ctrl_dt, u, in.s.w, L, act);
         else yank_omega_control(c, (T)ctrl_dt, u, thr, in.s.w, L, act);
       }
+      // (compensated storage and RK4 form their own thrust direction: there the frame serves the controller and the row only)
       if (comp) aviary_step_comp<T, RK4, DRAG>(c, in.s, in.r, act, prev, clipped);
+      else if (CTRL == 0) aviary_step<T, RK4, DRAG>(c, in.s, F, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, in.s, act, prev, clipped);
       if (CTRL == 3)
         for (int j = 0; j < 4; ++j) thr[j] = clipped[j];
-      if (want) pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
+      if (kCarry) {
+        F = make_frame(in.s.q, in.s.w);
+        if (want) pack_obs(in.s, F, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
+      } else if (want) {
+        pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
+      }
       // the clipped RPM leaves with the last step (not carried to the end of the loop)
       if (last && (DRAG || last_rpm)) {
         unsigned iu = (unsigned)i;

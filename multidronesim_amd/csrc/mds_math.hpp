@@ -182,36 +182,60 @@ template <typename T> struct State {
 // [UPSTREAM] p.getMatrixFromQuaternion (btMatrix3x3::setRotation, s = 2/|q|^2).  Scale
 // invariant, so it also equals scipy Rotation.from_quat(q).as_matrix() used by
 // model_conversions.py:110.
-template <typename T> MDS_HD M3<T> quat_to_rot(const T q[4]) {
+// Every sum of two products is an explicit FMA: the entries feed the controller, the thrust direction and the Euler angles of
+// both launch forms, which must agree to the bit (left to contraction, which product is rounded first differs between kernels).
+// *r22m1 = R22 - 1 = -s (xx + yy) without the cancellation of forming R.m[8] - 1.
+template <typename T> MDS_HD M3<T> quat_to_rot_m1(const T q[4], T* r22m1) {
   const T x = q[0], y = q[1], z = q[2], w = q[3];
   const T d = m_fma(x, x, m_fma(y, y, m_fma(z, z, w * w)));
   const T s = T(2) * m_rcp(d);
   const T xs = x * s, ys = y * s, zs = z * s;
   const T wx = w * xs, wy = w * ys, wz = w * zs;
-  const T xx = x * xs, xy = x * ys, xz = x * zs;
-  const T yy = y * ys, yz = y * zs, zz = z * zs;
+  const T yy = y * ys, zz = z * zs;
+  const T xx_yy = m_fma(x, xs, yy), xx_zz = m_fma(x, xs, zz), yy_zz = m_fma(y, ys, zz);
   M3<T> R;
-  R.m[0] = T(1) - (yy + zz);
-  R.m[1] = xy - wz;
-  R.m[2] = xz + wy;
-  R.m[3] = xy + wz;
-  R.m[4] = T(1) - (xx + zz);
-  R.m[5] = yz - wx;
-  R.m[6] = xz - wy;
-  R.m[7] = yz + wx;
-  R.m[8] = T(1) - (xx + yy);
+  R.m[0] = T(1) - yy_zz;
+  R.m[1] = m_fma(x, ys, -wz);
+  R.m[2] = m_fma(x, zs, wy);
+  R.m[3] = m_fma(x, ys, wz);
+  R.m[4] = T(1) - xx_zz;
+  R.m[5] = m_fma(y, zs, -wx);
+  R.m[6] = m_fma(x, zs, -wy);
+  R.m[7] = m_fma(y, zs, wx);
+  R.m[8] = T(1) - xx_yy;
+  *r22m1 = -xx_yy;
   return R;
 }
-
-// R(q) v for a (near-)unit quaternion without forming R: v + 2 q_w (q_v x v) + 2 q_v x (q_v x v),
-// scaled by 1/|q|^2 like quat_to_rot.
-template <typename T> MDS_HD V3<T> quat_rotate(const T q[4], V3<T> v) {
-  const V3<T> qv = {q[0], q[1], q[2]};
-  const T s = T(2) * m_rcp(m_fma(q[0], q[0], m_fma(q[1], q[1], m_fma(q[2], q[2], q[3] * q[3]))));
-  const V3<T> t = s * cross(qv, v);
-  const V3<T> u = cross(qv, t);
-  return {m_fma(q[3], t.x, v.x) + u.x, m_fma(q[3], t.y, v.y) + u.y, m_fma(q[3], t.z, v.z) + u.z};
+template <typename T> MDS_HD M3<T> quat_to_rot(const T q[4]) {
+  T r22m1;
+  return quat_to_rot_m1(q, &r22m1);
 }
+
+// The rotation frame of one state: everything a control step derives from (q, w) -- the controller's R and world-frame rate,
+// the thrust direction of the rigid-body step (R's third column, less e3), the observation's Euler angles and ang_v.  Formed
+// once per state by make_frame; the whole-rollout loop carries the frame of the state after step k into step k + 1.
+template <typename T> struct Frame {
+  M3<T> R;
+  T r22m1;     // R22 - 1
+  V3<T> av;    // R w, the world-frame rate
+};
+template <typename T> MDS_HD Frame<T> make_frame(const T q[4], V3<T> w) {
+  Frame<T> F;
+  F.R = quat_to_rot_m1(q, &F.r22m1);
+  F.av = mul(F.R, w);
+  return F;
+}
+// (r02, r12, r22 - 1): what body_accel needs of the attitude
+template <typename T> MDS_HD V3<T> thrust_dir(const Frame<T>& F) { return {F.R.m[2], F.R.m[5], F.r22m1}; }
+template <typename T> MDS_HD V3<T> thrust_dir(const T q[4]) {
+  T r22m1;
+  const M3<T> R = quat_to_rot_m1(q, &r22m1);
+  return {R.m[2], R.m[5], r22m1};
+}
+
+// R(q) v, by the same matrix as make_frame: quat_rotate(q, w) is the frame's av to the bit (the LQR controllers read it where the
+// observation's consumer reads o[13..15]).
+template <typename T> MDS_HD V3<T> quat_rotate(const T q[4], V3<T> v) { return mul(quat_to_rot(q), v); }
 
 // [UPSTREAM] p.getQuaternionFromEuler (btQuaternion::setEulerZYX)
 template <typename T> MDS_HD void quat_from_euler(T roll, T pitch, T yaw, T q[4]) {
@@ -225,25 +249,23 @@ template <typename T> MDS_HD void quat_from_euler(T roll, T pitch, T yaw, T q[4]
   q[3] = cr * cp * cy + sr * sp * sy;
 }
 
-// [UPSTREAM] p.getEulerFromQuaternion incl. the +-0.99999 gimbal branches
-template <typename T> MDS_HD V3<T> euler_from_quat(const T q[4]) {
-  const T x = q[0], y = q[1], z = q[2], w = q[3];
-  const T sqx = x * x, sqy = y * y, sqz = z * z, squ = w * w;
-  // (the three sums of two products below are written with the FMA the compiler picks for them in the step kernels: left to
-  // contraction, which of the two products is rounded first differs from one kernel to the next, and with it the last bit of the angle)
-  const T sarg = T(-2) * m_fma(x, z, -(w * y));
+// [UPSTREAM] p.getEulerFromQuaternion incl. the +-0.99999 gimbal branches, from the rotation matrix of the same quaternion:
+// 2 (yz + wx) = R21, ww - xx - yy + zz = R22 |q|^2, -2 (xz - wy) = -R20, 2 (wz + xy) = R10, ww + xx - yy - zz = R00 |q|^2
+// (atan2 does not see the common factor; R is scale invariant where Bullet's expressions assume a unit quaternion).
+// The gimbal arms keep Bullet's quaternion form; they select the atan2 arguments, so that two atan2 bodies serve all three arms.
+template <typename T> MDS_HD V3<T> rpy_from_rot(const M3<T>& R, const T q[4]) {
+  const T sarg = -R.m[6];
+  const bool lo = sarg <= T(-0.99999), hi = sarg >= T(0.99999), gimbal = lo || hi;
+  const T ry = gimbal ? T(0) : R.m[7], rx = gimbal ? T(1) : R.m[8];
+  const T yy = lo ? q[0] : hi ? -q[0] : R.m[3], yx = lo ? -q[1] : hi ? q[1] : R.m[0];
+  const T yaw = m_atan2(yy, yx);
   V3<T> rpy;
-  if (sarg <= T(-0.99999)) {
-    rpy = {T(0), T(-1.57079632679489661923), T(2) * m_atan2(x, -y)};
-  } else if (sarg >= T(0.99999)) {
-    rpy = {T(0), T(1.57079632679489661923), T(2) * m_atan2(-x, y)};
-  } else {
-    rpy.x = m_atan2(T(2) * m_fma(y, z, w * x), squ - sqx - sqy + sqz);
-    rpy.y = m_asin(sarg);
-    rpy.z = m_atan2(T(2) * m_fma(w, z, x * y), squ + sqx - sqy - sqz);
-  }
+  rpy.x = m_atan2(ry, rx);
+  rpy.y = lo ? T(-1.57079632679489661923) : hi ? T(1.57079632679489661923) : m_asin(sarg);
+  rpy.z = gimbal ? T(2) * yaw : yaw;
   return rpy;
 }
+template <typename T> MDS_HD V3<T> euler_from_quat(const T q[4]) { return rpy_from_rot(quat_to_rot(q), q); }
 
 // [UPSTREAM] _dynamics: thrust (body z) and body torques from 4 clipped RPM.
 // Same quantities, conditioned for fp32: differences of squares are formed as
@@ -269,12 +291,10 @@ template <typename T> MDS_HD void rotor_wrench(const Consts<T>& c, const T rpm[4
 // linear + angular acceleration of the rigid body (shared by Euler and RK4).
 // force_world = R [0,0,T] - [0,0,MG] with T = MG + excess:  f_z = (R33 - 1) T + excess.
 template <typename T, bool DRAG>
-MDS_HD void body_accel(const Consts<T>& c, const T q[4], V3<T> vel, V3<T> w, T thrust_excess, V3<T> tau, const T drag_s,
+MDS_HD void body_accel(const Consts<T>& c, V3<T> dir, V3<T> vel, V3<T> w, T thrust_excess, V3<T> tau, const T drag_s,
                        V3<T>* acc, V3<T>* wdot) {
-  const T x = q[0], y = q[1], z = q[2], ww = q[3];
-  const T s = T(2) * m_rcp(m_fma(x, x, m_fma(y, y, m_fma(z, z, ww * ww))));
   const T thrust = c.gravity + thrust_excess;
-  const T r02 = s * m_fma(x, z, ww * y), r12 = s * m_fma(y, z, -(ww * x)), r22m1 = -s * m_fma(x, x, y * y);
+  const T r02 = dir.x, r12 = dir.y, r22m1 = dir.z;    // thrust_dir of the attitude
   V3<T> f = {m_fma(r02, thrust, c.wind[0]), m_fma(r12, thrust, c.wind[1]), m_fma(r22m1, thrust, thrust_excess) + c.wind[2]};
   if (DRAG) {  // [UPSTREAM] _drag: world force -c (.) sum(2 pi rpm_prev/60) (.) v_world
     f.x = m_fma(-c.drag[0] * drag_s, vel.x, f.x);
@@ -285,6 +305,11 @@ MDS_HD void body_accel(const Consts<T>& c, const T q[4], V3<T> vel, V3<T> w, T t
   const V3<T> Jw = {c.J[0] * w.x, c.J[1] * w.y, c.J[2] * w.z};
   const V3<T> t = tau - cross(w, Jw);
   *wdot = {t.x * c.invJ[0], t.y * c.invJ[1], t.z * c.invJ[2]};
+}
+template <typename T, bool DRAG>
+MDS_HD void body_accel(const Consts<T>& c, const T q[4], V3<T> vel, V3<T> w, T thrust_excess, V3<T> tau, const T drag_s,
+                       V3<T>* acc, V3<T>* wdot) {
+  body_accel<T, DRAG>(c, thrust_dir(q), vel, w, thrust_excess, tau, drag_s, acc, wdot);
 }
 
 // [UPSTREAM] _integrateQ (exact exponential for a constant body rate); identity for
@@ -311,20 +336,28 @@ template <typename T> MDS_HD void integrate_q(T q[4], V3<T> w, T dt) {
 }
 
 // [UPSTREAM] _dynamics, Physics.DYN: explicit Euler on (v, omega); p with NEW v, q with NEW omega
+// (dir: thrust_dir of s.q, from the caller's frame where it holds one)
 template <typename T, bool DRAG>
-MDS_HD void step_euler_wrench(const Consts<T>& c, State<T>& s, T thrust, V3<T> tau, T drag_s) {
+MDS_HD void step_euler_wrench(const Consts<T>& c, State<T>& s, V3<T> dir, T thrust, V3<T> tau, T drag_s) {
   V3<T> acc, wdot;
-  body_accel<T, DRAG>(c, s.q, s.v, s.w, thrust, tau, drag_s, &acc, &wdot);
+  body_accel<T, DRAG>(c, dir, s.v, s.w, thrust, tau, drag_s, &acc, &wdot);
   s.v = {m_fma(c.dt, acc.x, s.v.x), m_fma(c.dt, acc.y, s.v.y), m_fma(c.dt, acc.z, s.v.z)};
   s.w = {m_fma(c.dt, wdot.x, s.w.x), m_fma(c.dt, wdot.y, s.w.y), m_fma(c.dt, wdot.z, s.w.z)};
   s.p = {m_fma(c.dt, s.v.x, s.p.x), m_fma(c.dt, s.v.y, s.p.y), m_fma(c.dt, s.v.z, s.p.z)};
   integrate_q(s.q, s.w, c.dt);
 }
-template <typename T, bool DRAG> MDS_HD void step_euler(const Consts<T>& c, State<T>& s, const T rpm[4], T drag_s) {
+template <typename T, bool DRAG>
+MDS_HD void step_euler_wrench(const Consts<T>& c, State<T>& s, T thrust, V3<T> tau, T drag_s) {
+  step_euler_wrench<T, DRAG>(c, s, thrust_dir(s.q), thrust, tau, drag_s);
+}
+template <typename T, bool DRAG> MDS_HD void step_euler(const Consts<T>& c, State<T>& s, V3<T> dir, const T rpm[4], T drag_s) {
   T thrust;
   V3<T> tau;
   rotor_wrench(c, rpm, &thrust, &tau);
-  step_euler_wrench<T, DRAG>(c, s, thrust, tau, drag_s);
+  step_euler_wrench<T, DRAG>(c, s, dir, thrust, tau, drag_s);
+}
+template <typename T, bool DRAG> MDS_HD void step_euler(const Consts<T>& c, State<T>& s, const T rpm[4], T drag_s) {
+  step_euler<T, DRAG>(c, s, thrust_dir(s.q), rpm, drag_s);
 }
 
 // ------------------------------------------------------------------------------------
@@ -497,6 +530,23 @@ MDS_HD void aviary_step(const Consts<T>& c, State<T>& s, const T action[4], T rp
   }
 }
 
+// The same step for a caller that holds the frame of s: the first substep takes its thrust direction from F (RK4 forms its own
+// at every stage), later substeps form it from the new attitude -- thrust_dir(q) is thrust_dir(make_frame(q, .)) to the bit.
+template <typename T, bool RK4, bool DRAG>
+MDS_HD void aviary_step(const Consts<T>& c, State<T>& s, const Frame<T>& F, const T action[4], T rpm_prev[4], T clipped[4]) {
+  for (int i = 0; i < 4; ++i) clipped[i] = m_clamp(action[i], T(0), c.max_rpm);
+  V3<T> dir = thrust_dir(F);
+  for (int k = 0; k < c.substeps; ++k) {
+    T drag_s = T(0);
+    if (DRAG) drag_s = T(0.10471975511965977462) * ((rpm_prev[0] + rpm_prev[1]) + (rpm_prev[2] + rpm_prev[3]));
+    if (RK4) step_rk4<T, DRAG>(c, s, clipped, drag_s);
+    else step_euler<T, DRAG>(c, s, dir, clipped, drag_s);
+    if (!RK4 && k + 1 < c.substeps) dir = thrust_dir(s.q);
+    if (DRAG)
+      for (int i = 0; i < 4; ++i) rpm_prev[i] = clipped[i];
+  }
+}
+
 template <typename T, bool DRAG> MDS_HD void step_rk4_comp(const Consts<T>& c, State<T>& s, Resid<T>& r, const T rpm[4], T drag_s) {
   T thrust;
   V3<T> tau;
@@ -534,15 +584,19 @@ MDS_HD void aviary_step_comp(const Consts<T>& c, State<T>& s, Resid<T>& r, const
 
 // [UPSTREAM] _getDroneStateVector: pos3 | quat4 xyzw | rpy3 | vel3 | ang_v3 (world) | last_clipped_action4.
 // ang_v = R(q) w: upstream hands Bullet R(q_before) w, identical because Exp(w dt) w = w.
-template <typename T> MDS_HD void pack_obs(const State<T>& s, V3<T> origin, const T rpm[4], T o[20]) {
-  const V3<T> av = quat_rotate(s.q, s.w);
-  const V3<T> rpy = euler_from_quat(s.q);
+// F: the frame of s (make_frame(s.q, s.w)).
+template <typename T> MDS_HD void pack_obs(const State<T>& s, const Frame<T>& F, V3<T> origin, const T rpm[4], T o[20]) {
+  const V3<T> av = F.av;
+  const V3<T> rpy = rpy_from_rot(F.R, s.q);
   o[0] = s.p.x + origin.x; o[1] = s.p.y + origin.y; o[2] = s.p.z + origin.z;
   o[3] = s.q[0]; o[4] = s.q[1]; o[5] = s.q[2]; o[6] = s.q[3];
   o[7] = rpy.x; o[8] = rpy.y; o[9] = rpy.z;
   o[10] = s.v.x; o[11] = s.v.y; o[12] = s.v.z;
   o[13] = av.x; o[14] = av.y; o[15] = av.z;
   o[16] = rpm[0]; o[17] = rpm[1]; o[18] = rpm[2]; o[19] = rpm[3];
+}
+template <typename T> MDS_HD void pack_obs(const State<T>& s, V3<T> origin, const T rpm[4], T o[20]) {
+  pack_obs(s, make_frame(s.q, s.w), origin, rpm, o);
 }
 
 // ------------------------------------------------------------------------------------
@@ -570,8 +624,8 @@ template <typename T> MDS_HD Desired<T> lemniscate_local(const LemniscateParams<
   d.v = {-aw * (s2 * s2 + s2 + (s2 - T(1)) * c2) * inv2, -aw * s * (s2 + T(2) * c2 + T(1)) * inv2, T(0)};
   // sin 2th, cos 2th, cos 4th by double angle (the reference calls sin/cos on 2th, 4th)
   const T sin2 = T(2) * s * c, cos2 = c2 - s2, cos4 = T(1) - T(2) * sin2 * sin2;
-  const T e = cos2 - T(3);
-  const T inv3 = m_rcp(e * e * e);
+  // cos 2th - 3 = -2 (1 + sin^2 th) = -2 den: 1 / (cos 2th - 3)^3 = -inv^3 / 8
+  const T inv3 = T(-0.125) * (inv2 * inv);
   const T aw2 = aw * P.omega;
   d.a = {T(4) * aw2 * sin2 * (T(3) * cos2 + T(7)) * inv3, aw2 * c * (T(44) * cos2 + cos4 - T(21)) * inv3, T(0)};
   T sy = T(0), cy = T(1);
