@@ -85,6 +85,19 @@ MDS_HD void m_sincos(double x, double* s, double* c) {
   *c = cos(x);
 }
 
+// sin/cos of an argument in [-pi/4, pi/4]: the two short minimax polynomials m_sincos ends in.
+MDS_HD void m_sincos_reduced(float r, float* s, float* c) {
+  const float r2 = r * r;
+  // sin(r) ~ r + r^3 * P(r^2), cos(r) ~ 1 - r^2/2 + r^4 * Q(r^2)
+  float ps = fmaf(r2, 2.6083159809786593541503e-06f, -1.981069071916863322258e-04f);
+  ps = fmaf(ps, r2, 8.333078585565090179443e-03f);
+  ps = fmaf(ps, r2, -1.666665971279144287109e-01f);
+  *s = fmaf(ps * r2, r, r);
+  float pc = fmaf(r2, 2.443315711809948e-05f, -1.388731625493765e-03f);
+  pc = fmaf(pc, r2, 4.166664568298827e-02f);
+  *c = fmaf(pc * r2, r2, fmaf(r2, -0.5f, 1.0f));
+}
+
 // sin/cos of an argument ALREADY reduced to about [-pi, pi] (callers reduce phases in
 // double): one more Cody-Waite step to [-pi/4, pi/4] and two short minimax polynomials.
 // Max error < 1.5 ulp on the reduced range; ~25 VALU ops instead of ocml's generic path.
@@ -94,21 +107,29 @@ MDS_HD void m_sincos(float x, float* s, float* c) {
   float r = fmaf(k, -1.57079601287841796875f, x);
   r = fmaf(k, -3.1391647326017846353352069854736328125e-7f, r);
   r = fmaf(k, -5.390302529957764765544e-15f, r);
-  const float r2 = r * r;
-  // sin(r) ~ r + r^3 * P(r^2), cos(r) ~ 1 - r^2/2 + r^4 * Q(r^2)
-  float ps = fmaf(r2, 2.6083159809786593541503e-06f, -1.981069071916863322258e-04f);
-  ps = fmaf(ps, r2, 8.333078585565090179443e-03f);
-  ps = fmaf(ps, r2, -1.666665971279144287109e-01f);
-  const float sr = fmaf(ps * r2, r, r);
-  float pc = fmaf(r2, 2.443315711809948e-05f, -1.388731625493765e-03f);
-  pc = fmaf(pc, r2, 4.166664568298827e-02f);
-  const float cr = fmaf(pc * r2, r2, fmaf(r2, -0.5f, 1.0f));
+  float sr, cr;
+  m_sincos_reduced(r, &sr, &cr);
   const int q = (int)k & 3;
   const float ss = (q & 1) ? cr : sr;
   const float cc = (q & 1) ? sr : cr;
   *s = (q & 2) ? -ss : ss;
   *c = ((q + 1) & 2) ? -cc : cc;
 }
+
+// sin/cos of an angle that is small in practice (half the turn of one physics substep, |w| dt / 2: 0.05 rad at 10 rad/s and 100 Hz).
+// For 0 < |x| <= 0.75 m_sincos rounds k to 0, its three Cody-Waite steps return x itself and every quadrant select keeps its first
+// arm: m_sincos_reduced(x) is m_sincos(x) to the bit (x = -0 alone differs, in the sign of the zero sine; no caller forms it).
+// The short path is taken when no lane of the wave is above the threshold -- a scalar branch -- and the general one otherwise.
+MDS_HD void m_sincos_small(float x, float* s, float* c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const bool small = __builtin_amdgcn_ballot_w64(!(fabsf(x) <= 0.75f)) == 0;
+#else
+  const bool small = fabsf(x) <= 0.75f;
+#endif
+  if (small) m_sincos_reduced(x, s, c);
+  else m_sincos(x, s, c);
+}
+MDS_HD void m_sincos_small(double x, double* s, double* c) { m_sincos(x, s, c); }
 
 // phase = a*t + b reduced to [-pi, pi], formed in double so that a 30 s horizon does not
 // cost the fp32 path 1e-6 rad of phase (t is passed as double through the C-ABI).
@@ -132,7 +153,11 @@ template <typename T> MDS_HD V3<T> cross(V3<T> a, V3<T> b) {
   return {m_fma(a.y, b.z, -(a.z * b.y)), m_fma(a.z, b.x, -(a.x * b.z)), m_fma(a.x, b.y, -(a.y * b.x))};
 }
 template <typename T> MDS_HD T norm(V3<T> a) { return m_sqrt(dot(a, a)); }
-
+// (a x b) x a for a UNIT vector a: the part of b at right angles to a, b - (a . b) a -- one dot and three FMAs for two cross products
+template <typename T> MDS_HD V3<T> reject(V3<T> b, V3<T> a) {
+  const T d = -dot(a, b);
+  return {m_fma(d, a.x, b.x), m_fma(d, a.y, b.y), m_fma(d, a.z, b.z)};
+}
 // row-major 3x3
 template <typename T> struct M3 {
   T m[9];
@@ -320,7 +345,7 @@ template <typename T> MDS_HD void integrate_q(T q[4], V3<T> w, T dt) {
   const T inv_wn = m_rsqrt(w2);
   const T wn = w2 * inv_wn;
   T st, ct;
-  m_sincos(wn * dt * T(0.5), &st, &ct);
+  m_sincos_small(wn * dt * T(0.5), &st, &ct);     // > 0: wn > 1e-8
   const T k = st * inv_wn;
   const T x = q[0], y = q[1], z = q[2], ww = q[3];
   const T p = w.x, qq = w.y, r = w.z;
@@ -405,7 +430,7 @@ template <typename T> MDS_HD void integrate_q_comp(T q[4], T rq[4], V3<T> w, T d
   const T inv_wn = m_rsqrt(w2);
   const T wn = w2 * inv_wn;
   T st, ct;
-  m_sincos(wn * dt * T(0.5), &st, &ct);
+  m_sincos_small(wn * dt * T(0.5), &st, &ct);     // > 0: wn > 1e-8
   const T k = st * inv_wn;
   const T cm1 = -(st * st) * m_rcp(T(1) + ct);
   const T x = q[0], y = q[1], z = q[2], ww = q[3];
@@ -702,13 +727,12 @@ MDS_HD void geometric_control(const Consts<T>& c, V3<T> p_rel, const M3<T>& R, V
   const V3<T> c1 = cross(b3d, b1c);
   const T inv_n1 = m_rsqrt(dot(c1, c1));
   const V3<T> b2d = inv_n1 * c1;
-  const V3<T> c2 = cross(b2d, b3d);
-  const V3<T> b1d = m_rsqrt(dot(c2, c2)) * c2;                          // :91
+  const V3<T> b1d = cross(b2d, b3d);                                    // :91; orthonormal b2d, b3d: already a unit vector
   const V3<T> b1c_dot = {-sy * des.yaw_rate, cy * des.yaw_rate, T(0)};  // :95
   const V3<T> f_dot = (c.mass * inv_fn) * mul(R, hadamard(Kp, ev));     // :96
-  const V3<T> b3d_dot = cross(cross(b3d, f_dot), b3d);                  // :97
+  const V3<T> b3d_dot = reject(f_dot, b3d);                             // :97
   const V3<T> inner = inv_n1 * (cross(b1c_dot, b3d) + cross(b1c, b3d_dot));       // |b1c x b3d| = |b3d x b1c|
-  const V3<T> b2d_dot = cross(cross(b2d, inner), b2d);                  // :98-99
+  const V3<T> b2d_dot = reject(inner, b2d);                             // :98-99
   const V3<T> b1d_dot = cross(b3d_dot, b2d) + cross(b3d, b2d_dot);      // :100
   // W = R_des @ R_dot_des (no-op transpose, :102); w_des = (W21, W02, W10) (:103)
   const V3<T> w_des = {m_fma(b1d.z, b2d_dot.x, m_fma(b2d.z, b2d_dot.y, b3d.z * b2d_dot.z)),
