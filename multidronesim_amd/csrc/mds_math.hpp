@@ -53,12 +53,50 @@ MDS_HD double m_exp(double x) { return exp(x); }
 MDS_HD float m_abs(float x) { return fabsf(x); }
 MDS_HD double m_abs(double x) { return fabs(x); }
 MDS_HD double m_atan2(double y, double x) { return atan2(y, x); }
+// The lanes of the wave in which `c` holds, as a mask (0 when there is none).  On the device a scalar value, so a branch on it is a
+// scalar branch and not an exec-masked arm: a wave does not execute the side it skips.  On the host, the value's own `c`.
+// The short arms below are taken when no lane of the wave fails their test; each gives the bits of the general arm it stands in
+// for, so a lane's result does not depend on the company it keeps in its wave.
+MDS_HD uint64_t m_lanes(bool c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ballot_w64(c);
+#else
+  return c;
+#endif
+}
+MDS_HD bool m_wave_all(bool ok) { return m_lanes(!ok) == 0; }
+// Inside the `if` on such a flag around the few instructions a short arm skips: an empty volatile asm, which the compiler may not
+// execute speculatively -- the `if` stays the scalar branch it is meant to be where it would otherwise become a row of selects that
+// every wave pays for.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MDS_KEEP_BRANCH() asm volatile("")
+#else
+#define MDS_KEEP_BRANCH() ((void)0)
+#endif
+// !(0 < x < inf) (one v_cmp_class_f32: everything but +denormal and +normal)
+MDS_HD bool m_not_pos_finite(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_classf(x, 0x27f);
+#else
+  return !(x > 0.0f && x < INFINITY);
+#endif
+}
+// (y, x) in the first or the eighth octant, 0 < x < inf and |y| <= x (false for a NaN or an infinity in either); and the lanes of the
+// wave where it fails (one mask per compare, joined on the scalar side)
+MDS_HD bool m_atan2_in_octant(float y, float x) { return !m_not_pos_finite(x) & (x >= fabsf(y)); }
+MDS_HD uint64_t m_atan2_lanes_out_of_octant(float y, float x) { return m_lanes(m_not_pos_finite(x)) | m_lanes(!(x >= fabsf(y))); }
 // fp32 atan2: octant reduction to a = min/max in [0,1], one near-minimax odd polynomial of
-// degree 17 (max error 1e-7 rad incl. fp32 evaluation), ~25 VALU ops vs ocml's ~45.
-MDS_HD float m_atan2(float y, float x) {
+// degree 17 (max error 1e-7 rad incl. fp32 evaluation), ~25 VALU ops vs ocml's ~45.  In three parts, so that a caller with several
+// angles can put the parts of each side by side: atan2(y, x) = copysign(fix(core(reduce(y, x)), y, x), y).
+// reduce: mn = min(|x|, |y|), mx = max(|x|, |y|)
+MDS_HD void m_atan2_reduce(float y, float x, float* mn, float* mx) {
   const float ax = fabsf(x), ay = fabsf(y);
-  const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-  const float a = mx > 0.0f ? mn * m_rcp(mx) : 0.0f;
+  *mx = fmaxf(ax, ay);
+  *mn = fminf(ax, ay);
+}
+// atan(mn / mx) in [-pi/4, pi/4]: odd in mn to the bit (the quotient carries the sign, the polynomial sees its square)
+MDS_HD float m_atan2_core(float mn, float mx) {
+  const float a = mn * m_rcp(mx);
   const float z = a * a;
   float p = 2.4567161705e-03f;
   p = fmaf(p, z, -1.4401325081e-02f);
@@ -69,12 +107,62 @@ MDS_HD float m_atan2(float y, float x) {
   p = fmaf(p, z, 1.9985906696e-01f);
   p = fmaf(p, z, -3.3332597024e-01f);
   p = fmaf(p, z, 9.9999988638e-01f);
-  float r = p * a;
-  r = ay > ax ? 1.57079632679489661923f - r : r;
-  r = x < 0.0f ? 3.14159265358979323846f - r : r;
-  return copysignf(r, y);
+  return p * a;
 }
+// from the octant to the half plane y >= 0; atan2(+-0, +-0) = +-0 or +-pi (the core's 0 * rcp(0) is set to the 0 it stands for)
+MDS_HD float m_atan2_fix(float r, float mx, float y, float x) {
+  r = mx > 0.0f ? r : 0.0f;
+  r = fabsf(y) > fabsf(x) ? 1.57079632679489661923f - r : r;
+  return x < 0.0f ? 3.14159265358979323846f - r : r;
+}
+// octant: the caller's word, the same for the whole wave, that m_atan2_in_octant(y, x) holds.  Then min = |y|, max = x > 0 and the
+// fix keeps its first arm three times: the reduction, the fix and the copysign are skipped -- the core of the signed y is the
+// copysign of the core of |y| -- the core is the same instructions for both arms, and so are the bits.
+MDS_HD float m_atan2_arm(float y, float x, bool octant) {
+  float mn = y, mx = x;
+  if (!octant) {
+    MDS_KEEP_BRANCH();
+    m_atan2_reduce(y, x, &mn, &mx);
+  }
+  float r = m_atan2_core(mn, mx);
+  if (!octant) {
+    MDS_KEEP_BRANCH();
+    r = copysignf(m_atan2_fix(r, mx, y, x), y);
+  }
+  return r;
+}
+MDS_HD float m_atan2(float y, float x) { return m_atan2_arm(y, x, m_atan2_lanes_out_of_octant(y, x) == 0); }
+// fp32 asin, ocml's asinf restated operation for operation (the same bits on the device, checked over [-1, 1]) so that its
+// polynomial can be reached without the range arms: x + x^3 P(x^2) below 0.5, pi/2 - 2 asin(sqrt((1 - |x|) / 2)) with the same P
+// from there on.  small: the caller's word, the same for the whole wave, that x * x < 0.25 (which implies |x| < 0.5: every select
+// keeps the first form, and the square root is not needed).  The host build keeps libm's asinf in m_asin.
+MDS_HD float m_asin_arm(float x, bool small) {
+  const float ax = fabsf(x), x2 = x * x;
+  float r = x2;
+  if (!small) {
+    MDS_KEEP_BRANCH();
+    r = ax >= 0.5f ? fmaf(ax, -0.5f, 0.5f) : x2;
+  }
+  float p = fmaf(r, 0x1.38434ep-5f, 0x1.bf8bb4p-7f);
+  p = fmaf(r, p, 0x1.069878p-5f);
+  p = fmaf(r, p, 0x1.6c8362p-5f);
+  p = fmaf(r, p, 0x1.33379p-4f);
+  p = fmaf(r, p, 0x1.555558p-3f);
+  const float u = r * p;
+  float ret = fmaf(x, u, x);      // copysign(fma(|x|, u, |x|), x) to the bit: the fma is odd in (x, x)
+  if (!small) {
+    MDS_KEEP_BRANCH();
+    const float s = m_sqrt(r);
+    const float wide = 0x1.921fb6p+0f - 2.0f * fmaf(s, u, s);
+    ret = ax < 0.5f ? ret : copysignf(wide, x);
+  }
+  return ret;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+MDS_HD float m_asin(float x) { return m_asin_arm(x, m_wave_all(x * x < 0.25f)); }
+#else
 MDS_HD float m_asin(float x) { return asinf(x); }
+#endif
 MDS_HD double m_asin(double x) { return asin(x); }
 template <typename T> MDS_HD T m_min(T a, T b) { return a < b ? a : b; }
 template <typename T> MDS_HD T m_max(T a, T b) { return a > b ? a : b; }
@@ -121,12 +209,7 @@ MDS_HD void m_sincos(float x, float* s, float* c) {
 // arm: m_sincos_reduced(x) is m_sincos(x) to the bit (x = -0 alone differs, in the sign of the zero sine; no caller forms it).
 // The short path is taken when no lane of the wave is above the threshold -- a scalar branch -- and the general one otherwise.
 MDS_HD void m_sincos_small(float x, float* s, float* c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const bool small = __builtin_amdgcn_ballot_w64(!(fabsf(x) <= 0.75f)) == 0;
-#else
-  const bool small = fabsf(x) <= 0.75f;
-#endif
-  if (small) m_sincos_reduced(x, s, c);
+  if (m_wave_all(fabsf(x) <= 0.75f)) m_sincos_reduced(x, s, c);
   else m_sincos(x, s, c);
 }
 MDS_HD void m_sincos_small(double x, double* s, double* c) { m_sincos(x, s, c); }
@@ -278,7 +361,7 @@ template <typename T> MDS_HD void quat_from_euler(T roll, T pitch, T yaw, T q[4]
 // 2 (yz + wx) = R21, ww - xx - yy + zz = R22 |q|^2, -2 (xz - wy) = -R20, 2 (wz + xy) = R10, ww + xx - yy - zz = R00 |q|^2
 // (atan2 does not see the common factor; R is scale invariant where Bullet's expressions assume a unit quaternion).
 // The gimbal arms keep Bullet's quaternion form; they select the atan2 arguments, so that two atan2 bodies serve all three arms.
-template <typename T> MDS_HD V3<T> rpy_from_rot(const M3<T>& R, const T q[4]) {
+template <typename T> MDS_HD V3<T> rpy_from_rot_arm(const M3<T>& R, const T q[4], bool) {
   const T sarg = -R.m[6];
   const bool lo = sarg <= T(-0.99999), hi = sarg >= T(0.99999), gimbal = lo || hi;
   const T ry = gimbal ? T(0) : R.m[7], rx = gimbal ? T(1) : R.m[8];
@@ -290,6 +373,42 @@ template <typename T> MDS_HD V3<T> rpy_from_rot(const M3<T>& R, const T q[4]) {
   rpy.z = gimbal ? T(2) * yaw : yaw;
   return rpy;
 }
+// fp32, the same in the parts of m_atan2.  plain: the caller's word, the same for the whole wave, that rpy_is_plain(R) holds -- no
+// gimbal arm, both atan2 in their octant.  Then every select of the gimbal chain keeps its matrix entry, and the chain, the two
+// reductions, the two fixes and the copysigns are skipped: one scalar branch around all that comes before the reciprocals and the
+// polynomials, one around all that comes after.
+template <> MDS_HD V3<float> rpy_from_rot_arm(const M3<float>& R, const float q[4], bool plain) {
+  const float sarg = -R.m[6];
+  float rmn = R.m[7], rmx = R.m[8], ymn = R.m[3], ymx = R.m[0];
+  float ry, rx, yy, yx;           // the atan2 arguments the gimbal chain selects: formed and read on the general path alone
+  bool lo, hi;
+  if (!plain) {
+    MDS_KEEP_BRANCH();
+    lo = sarg <= -0.99999f, hi = sarg >= 0.99999f;
+    ry = lo || hi ? 0.0f : R.m[7], rx = lo || hi ? 1.0f : R.m[8];
+    yy = lo ? q[0] : hi ? -q[0] : R.m[3], yx = lo ? -q[1] : hi ? q[1] : R.m[0];
+    m_atan2_reduce(ry, rx, &rmn, &rmx);
+    m_atan2_reduce(yy, yx, &ymn, &ymx);
+  }
+  float roll = m_atan2_core(rmn, rmx), yaw = m_atan2_core(ymn, ymx), pitch = m_asin(sarg);
+  if (!plain) {
+    MDS_KEEP_BRANCH();
+    roll = copysignf(m_atan2_fix(roll, rmx, ry, rx), ry);
+    yaw = copysignf(m_atan2_fix(yaw, ymx, yy, yx), yy);
+    pitch = lo || hi ? copysignf(1.57079632679489661923f, sarg) : pitch;
+    yaw = lo || hi ? 2.0f * yaw : yaw;
+  }
+  return {roll, pitch, yaw};
+}
+// No gimbal arm (|R20| < 0.99999) and both atan2 strictly inside their octant -- roll and yaw within 45 degrees, as in any normal
+// flight -- in every lane of the wave.  x > |y| is m_atan2_in_octant(y, x) less its edge |y| = x, but for x = +inf beside a finite y:
+// quat_to_rot forms no such entry (1 minus a square: at most 1, or NaN or -inf from a degenerate quaternion), and both arms would
+// give it the same bits.  One compare per angle, where the full test takes two.
+MDS_HD bool rpy_is_plain(const M3<float>& R) {
+  return (m_lanes(!(fabsf(R.m[6]) < 0.99999f)) | m_lanes(!(R.m[0] > fabsf(R.m[3]))) | m_lanes(!(R.m[8] > fabsf(R.m[7])))) == 0;
+}
+MDS_HD bool rpy_is_plain(const M3<double>&) { return false; }
+template <typename T> MDS_HD V3<T> rpy_from_rot(const M3<T>& R, const T q[4]) { return rpy_from_rot_arm(R, q, rpy_is_plain(R)); }
 template <typename T> MDS_HD V3<T> euler_from_quat(const T q[4]) { return rpy_from_rot(quat_to_rot(q), q); }
 
 // [UPSTREAM] _dynamics: thrust (body z) and body torques from 4 clipped RPM.
