@@ -927,7 +927,7 @@ __device__ __forceinline__ void cbf_filter_env(const CbfParams<T>& P, const int 
           const T um = c == 1 ? P.umax[1] : (c == 2 ? P.umax[2] : P.umax[3]);
           u = m_clamp(u, -um, um);
         } else {
-          u = m_clamp(u, swz[0][d], swz[1][d]);
+          u = m_min(m_max(u, swz[0][d]), swz[1][d]);      // (bounds computed per drone: they may cross, so not m_clamp)
         }
       }
       usafe[base * 4 + k] = (S)u;

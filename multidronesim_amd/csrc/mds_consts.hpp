@@ -43,6 +43,12 @@ template <typename T> inline void fill_consts(const mds_config& cfg, const mds_g
   c.inv_2L = (T)(1.0 / (2.0 * cfg.L));
   c.inv_4r = (T)(cfg.KF / (4.0 * cfg.KM));
   c.inv_kf = (T)(1.0 / cfg.KF);
+  // products of the rounded constants, in T and in the order of the device expressions they stand for (the same bits)
+  c.arm_kf = c.arm * c.kf;
+  c.arm_sqh_kf = c.arm * T(0.70710678118654752440) * c.kf;
+  c.kR_half[0] = T(-0.5) * c.kR[0];
+  c.kR_half[1] = T(0.5) * c.kR[1];
+  c.kR_half[2] = T(-0.5) * c.kR[2];
 }
 
 // [UPSTREAM] urdf <properties> (identical in cf2x.urdf and cf2p.urdf) and BaseAviary.__init__ GND_EFF_H_CLIP

@@ -166,7 +166,19 @@ MDS_HD float m_asin(float x) { return asinf(x); }
 MDS_HD double m_asin(double x) { return asin(x); }
 template <typename T> MDS_HD T m_min(T a, T b) { return a < b ? a : b; }
 template <typename T> MDS_HD T m_max(T a, T b) { return a > b ? a : b; }
+// m_clamp's bounds are constants of the launch: lo <= hi, neither a NaN (a caller whose bounds may cross or be NaN composes
+// m_min(m_max(x, lo), hi) itself).  Then the two selects are the median of (x, lo, hi) for every x -- a NaN x gives lo, -0 against
+// a +0 bound gives +0, either way -- and the fp32 device build takes it in one v_med3_f32, where the selects are two compares and
+// two v_cndmask each (the compiler cannot tell that a bound read from the kernel's arguments is no NaN).  The host build and
+// double keep the selects.
+// v_med3_f32 takes min3 of its operands when one is a NaN, and in IEEE mode min(sNaN, lo) is the quieted NaN, which the second min
+// drops for hi: a signalling NaN x would give hi where the selects give lo.  So x is canonicalised first.  That is an instruction
+// (v_max_f32 x, x, x) only where x may be a signalling NaN, i.e. comes straight from memory; the result of an arithmetic
+// instruction is canonical already and the compiler drops the call.
 template <typename T> MDS_HD T m_clamp(T x, T lo, T hi) { return m_min(m_max(x, lo), hi); }
+#if defined(__HIP_DEVICE_COMPILE__)
+MDS_HD float m_clamp(float x, float lo, float hi) { return __builtin_amdgcn_fmed3f(__builtin_canonicalizef(x), lo, hi); }
+#endif
 
 MDS_HD void m_sincos(double x, double* s, double* c) {
   *s = sin(x);
@@ -278,6 +290,11 @@ template <typename T> struct Consts {
   T max_motor_thrust;             // env.MAX_THRUST used per motor (sic)
   T inv_2L, inv_4r;               // closed-form inverse of the "+" mixer, r = KM/KF
   T inv_kf;
+  // Products of the constants above that a step would otherwise form on the vector pipe, every step (gfx9 has no scalar float
+  // unit).  Formed by fill_consts in T with the operation order of the device expression each replaces: the same bits.
+  T arm_kf;        // arm * kf: the "+" frame's torque arm
+  T arm_sqh_kf;    // arm * sqrt(1/2) * kf: the X frame's
+  T kR_half[3];    // -kR[0] / 2, kR[1] / 2, -kR[2] / 2: the signed halves of e_R's gains
 };
 
 template <typename T> struct State {
@@ -421,12 +438,16 @@ template <typename T> MDS_HD void rotor_wrench(const Consts<T>& c, const T rpm[4
   const T h = c.hover_rpm;
   *thrust_excess = m_fma(c.kf, (dsq(rpm[0], h) + dsq(rpm[1], h)) + (dsq(rpm[2], h) + dsq(rpm[3], h)), c.thrust_corr);
   tau->z = c.km * (dsq(rpm[1], rpm[0]) + dsq(rpm[3], rpm[2]));       // -z0 + z1 - z2 + z3
+  // the airframe is the same for the whole launch: a scalar branch, so that a handle executes its own arm alone (flattened into
+  // selects, every step paid for both); the arm lengths times kf come from the host (fill_consts)
   if (c.cf2x) {
-    const T l = c.arm * T(0.70710678118654752440) * c.kf;
+    MDS_KEEP_BRANCH();
+    const T l = c.arm_sqh_kf;
     tau->x = l * (dsq(rpm[0], rpm[2]) + dsq(rpm[1], rpm[3]));        // (f0 + f1 - f2 - f3) L/sqrt2
     tau->y = l * (dsq(rpm[1], rpm[0]) + dsq(rpm[2], rpm[3]));        // (-f0 + f1 + f2 - f3) L/sqrt2
   } else {
-    const T l = c.arm * c.kf;
+    MDS_KEEP_BRANCH();
+    const T l = c.arm_kf;
     tau->x = l * dsq(rpm[1], rpm[3]);                                 // (f1 - f3) L
     tau->y = l * dsq(rpm[2], rpm[0]);                                 // (-f0 + f2) L
   }
@@ -664,11 +685,16 @@ template <typename T, bool DRAG> MDS_HD void step_rk4(const Consts<T>& c, State<
 template <typename T, bool RK4, bool DRAG>
 MDS_HD void aviary_step(const Consts<T>& c, State<T>& s, const T action[4], T rpm_prev[4], T clipped[4]) {
   for (int i = 0; i < 4; ++i) clipped[i] = m_clamp(action[i], T(0), c.max_rpm);
+  // the wrench of the clipped RPM is the same in every substep: formed once, ahead of the loop, where rotor_wrench's branch on the
+  // airframe stands by itself (RK4 forms its own)
+  T thrust = T(0);
+  V3<T> tau = {T(0), T(0), T(0)};
+  if (!RK4) rotor_wrench(c, clipped, &thrust, &tau);
   for (int k = 0; k < c.substeps; ++k) {
     T drag_s = T(0);
     if (DRAG) drag_s = T(0.10471975511965977462) * ((rpm_prev[0] + rpm_prev[1]) + (rpm_prev[2] + rpm_prev[3]));
     if (RK4) step_rk4<T, DRAG>(c, s, clipped, drag_s);
-    else step_euler<T, DRAG>(c, s, clipped, drag_s);
+    else step_euler_wrench<T, DRAG>(c, s, thrust, tau, drag_s);
     if (DRAG)
       for (int i = 0; i < 4; ++i) rpm_prev[i] = clipped[i];
   }
@@ -680,11 +706,14 @@ template <typename T, bool RK4, bool DRAG>
 MDS_HD void aviary_step(const Consts<T>& c, State<T>& s, const Frame<T>& F, const T action[4], T rpm_prev[4], T clipped[4]) {
   for (int i = 0; i < 4; ++i) clipped[i] = m_clamp(action[i], T(0), c.max_rpm);
   V3<T> dir = thrust_dir(F);
+  T thrust = T(0);                 // (the wrench once, ahead of the substeps, as above)
+  V3<T> tau = {T(0), T(0), T(0)};
+  if (!RK4) rotor_wrench(c, clipped, &thrust, &tau);
   for (int k = 0; k < c.substeps; ++k) {
     T drag_s = T(0);
     if (DRAG) drag_s = T(0.10471975511965977462) * ((rpm_prev[0] + rpm_prev[1]) + (rpm_prev[2] + rpm_prev[3]));
     if (RK4) step_rk4<T, DRAG>(c, s, clipped, drag_s);
-    else step_euler<T, DRAG>(c, s, dir, clipped, drag_s);
+    else step_euler_wrench<T, DRAG>(c, s, dir, thrust, tau, drag_s);
     if (!RK4 && k + 1 < c.substeps) dir = thrust_dir(s.q);
     if (DRAG)
       for (int i = 0; i < 4; ++i) rpm_prev[i] = clipped[i];
@@ -801,8 +830,8 @@ template <typename T> MDS_HD void action_to_input(const Consts<T>& c, const T ac
   // difference of the RPMs is exact or rounded once, instead of the rounding of two ~0.07 N thrusts surviving in a ~1e-4 N difference
   // (fp32: 30x smaller error in tau / J downstream; the same identity the step kernel uses).  Mathematically the reference's mixer product.
   u[0] = c.kf * ((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]));
-  u[1] = (c.arm * c.kf) * ((r[1] - r[3]) * (r[1] + r[3]));
-  u[2] = (c.arm * c.kf) * ((r[2] - r[0]) * (r[2] + r[0]));
+  u[1] = c.arm_kf * ((r[1] - r[3]) * (r[1] + r[3]));
+  u[2] = c.arm_kf * ((r[2] - r[0]) * (r[2] + r[0]));
   u[3] = c.km * ((r[1] - r[0]) * (r[1] + r[0]) + (r[3] - r[2]) * (r[3] + r[2]));
 }
 
@@ -869,7 +898,7 @@ MDS_HD void geometric_control(const Consts<T>& c, V3<T> p_rel, const M3<T>& R, V
   const T E12 = dot(b2d, r2) - dot(b3d, r1);
   const T E02 = dot(b1d, r2) - dot(b3d, r0);
   const T E01 = dot(b1d, r1) - dot(b2d, r0);
-  const V3<T> eR = {T(-0.5) * c.kR[0] * E12, T(0.5) * c.kR[1] * E02, T(-0.5) * c.kR[2] * E01};
+  const V3<T> eR = {c.kR_half[0] * E12, c.kR_half[1] * E02, c.kR_half[2] * E01};        // (-1/2 kR0, 1/2 kR1, -1/2 kR2)
   const V3<T> Rdw = {m_fma(b1d.x, w_des.x, m_fma(b2d.x, w_des.y, b3d.x * w_des.z)),
                      m_fma(b1d.y, w_des.x, m_fma(b2d.y, w_des.y, b3d.y * w_des.z)),
                      m_fma(b1d.z, w_des.x, m_fma(b2d.z, w_des.y, b3d.z * w_des.z))};

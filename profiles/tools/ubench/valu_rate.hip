@@ -1,15 +1,28 @@
 // VALU issue-rate microbenchmark for gfx950: cycles per wave64 instruction for scalar and packed fp32, dependent and independent chains,
-// at 1..8 waves per SIMD.  Build: hipcc --offload-arch=gfx950 -O3 -o valu_rate valu_rate.hip ; run: ./valu_rate
+// and for the instruction classes the rollout step loop spends its slots on besides v_fma_f32 (compare-and-select pairs with their
+// hazard s_nop, v_med3_f32, v_max_f32 with an SGPR operand, v_mov_b32 from an SGPR, s_nop 1, v_rsq_f32, v_fma_f64), at 1..8 waves
+// per SIMD.  Build: hipcc --offload-arch=gfx950 -O3 -o valu_rate valu_rate.hip ; run: ./valu_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
 typedef float f2 __attribute__((ext_vector_type(2)));
 #define REP 256
-template <int MODE> __global__ void k(float* out, unsigned long long* cyc, int iters, float seed) {
+// one instruction (or one compare-and-select pair) on each of eight independent registers; the text is fixed, so the compiler
+// neither folds nor reorders it
+#define ASM8(text, ...)                                                                                                           \
+  asm volatile(text : "+v"(a0) : __VA_ARGS__); asm volatile(text : "+v"(a1) : __VA_ARGS__); asm volatile(text : "+v"(a2) : __VA_ARGS__);   \
+  asm volatile(text : "+v"(a3) : __VA_ARGS__); asm volatile(text : "+v"(a4) : __VA_ARGS__); asm volatile(text : "+v"(a5) : __VA_ARGS__);   \
+  asm volatile(text : "+v"(a6) : __VA_ARGS__); asm volatile(text : "+v"(a7) : __VA_ARGS__)
+template <int MODE> __global__ void k(float* out, unsigned long long* cyc, int iters, float seed, float slo, float shi) {
   float a0 = seed + threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
   f2 p0 = {a0, a1}, p1 = {a2, a3}, p2 = {a4, a5}, p3 = {a6, a7};
+  double d0 = a0, d1 = a1, d2 = a2, d3 = a3;
   const float m = 1.0000001f, c = 1e-9f;
   const f2 pm = {m, m}, pc = {c, c};
+  const double dm = 1.0000001, dc = 1e-9;
+  float vlo = slo;                                   // the bound a v_cndmask needs in a VGPR
+  asm volatile("" : "+v"(vlo));
+  asm volatile("" : "+s"(slo), "+s"(shi));           // ... and the same bounds as SGPR operands
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
   for (int it = 0; it < iters; ++it) {
 #pragma unroll
@@ -32,37 +45,66 @@ template <int MODE> __global__ void k(float* out, unsigned long long* cyc, int i
       } else if (MODE == 5) {  // two dependent scalar chains interleaved
         a0 = fmaf(a0, m, c); a1 = fmaf(a1, m, c); a0 = fmaf(a0, m, c); a1 = fmaf(a1, m, c);
         a0 = fmaf(a0, m, c); a1 = fmaf(a1, m, c); a0 = fmaf(a0, m, c); a1 = fmaf(a1, m, c);
+      } else if (MODE == 6) {  // x < lo ? lo : x as the compiler emits it back to back: v_cmp -> vcc, the hazard s_nop 1, v_cndmask (8 pairs)
+        ASM8("v_cmp_lt_f32_e32 vcc, %1, %0\n\ts_nop 1\n\tv_cndmask_b32_e32 %0, %2, %0, vcc", "s"(slo), "v"(vlo) : "vcc");
+      } else if (MODE == 7) {  // the same clamp in one v_med3_f32 (an inline constant and an SGPR bound)
+        ASM8("v_med3_f32 %0, %0, 0, %1", "s"(shi));
+      } else if (MODE == 8) {  // v_max_f32 with an SGPR operand
+        ASM8("v_max_f32_e32 %0, %1, %0", "s"(slo));
+      } else if (MODE == 9) {  // v_mov_b32 from an SGPR
+        ASM8("v_mov_b32_e32 %0, %1", "s"(slo));
+      } else if (MODE == 10) {  // s_nop 1 (counted as one instruction each)
+        asm volatile("s_nop 1\n\ts_nop 1\n\ts_nop 1\n\ts_nop 1\n\ts_nop 1\n\ts_nop 1\n\ts_nop 1\n\ts_nop 1");
+      } else if (MODE == 11) {  // v_rsq_f32, 8 independent
+        ASM8("v_rsq_f32_e32 %0, %0", "s"(slo));
+      } else if (MODE == 12) {  // v_fma_f64, 4 independent chains (8 instructions: two rounds)
+        d0 = fma(d0, dm, dc); d1 = fma(d1, dm, dc); d2 = fma(d2, dm, dc); d3 = fma(d3, dm, dc);
+        d0 = fma(d0, dm, dc); d1 = fma(d1, dm, dc); d2 = fma(d2, dm, dc); d3 = fma(d3, dm, dc);
+      } else if (MODE == 13) {  // the compare-and-select pair with two independent instructions between, as a scheduler would hide the hazard
+        ASM8("v_cmp_lt_f32_e32 vcc, %1, %0\n\tv_max_f32_e32 %0, %0, %0\n\tv_max_f32_e32 %0, %0, %0\n\tv_cndmask_b32_e32 %0, %2, %0, vcc", "s"(slo), "v"(vlo) : "vcc");
       }
     }
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + p0.x + p0.y + p1.x + p1.y + p2.x + p2.y + p3.x + p3.y;
+  out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + p0.x + p0.y + p1.x + p1.y + p2.x + p2.y + p3.x + p3.y +
+                                               (float)(d0 + d1 + d2 + d3);
   if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
 }
+// per: instructions issued per counted unit (a compare-and-select pair is one unit of 2 VALU + s_nop 1)
 template <int MODE> void run(const char* name, int waves_per_simd) {
-  const int block = 64 * 4 * (waves_per_simd > 4 ? 4 : waves_per_simd), cus = 256 * (waves_per_simd > 4 ? waves_per_simd / 4 : 1);   // workgroups of <= 16 waves, 4 SIMDs per CU
+  // workgroups of <= 16 waves on the 4 SIMDs of a CU: one per CU up to 4 waves per SIMD, two above
+  const int per_cu = waves_per_simd > 4 ? 2 : 1, block = 64 * 4 * waves_per_simd / per_cu, cus = 256 * per_cu;
   float* out; unsigned long long* cyc;
   hipMalloc(&out, sizeof(float) * cus * block); hipMalloc(&cyc, 8 * cus);
   const int iters = 200;
-  k<MODE><<<cus, block>>>(out, cyc, iters, 1.0f); hipDeviceSynchronize();
+  k<MODE><<<cus, block>>>(out, cyc, iters, 1.0f, 0.5f, 3.0e4f); hipDeviceSynchronize();
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  hipEventRecord(e0); k<MODE><<<cus, block>>>(out, cyc, iters, 1.0f); hipEventRecord(e1); hipEventSynchronize(e1);
+  hipEventRecord(e0); k<MODE><<<cus, block>>>(out, cyc, iters, 1.0f, 0.5f, 3.0e4f); hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   std::vector<unsigned long long> h(cus); hipMemcpy(h.data(), cyc, 8 * cus, hipMemcpyDeviceToHost);
   double mean = 0; for (auto v : h) mean += v; mean /= cus;
   const double instr = (double)iters * REP;   // per wave
-  printf("%-34s waves/SIMD %d: %.0f memtime ticks, %.3f ms -> %.2f ticks / instr / wave, %.2f ns * SIMD per instr\n", name, waves_per_simd, mean, ms,
+  printf("%-44s waves/SIMD %d: %.0f memtime ticks, %.3f ms -> %.2f ticks / instr / wave, %.2f ns * SIMD per instr\n", name, waves_per_simd, mean, ms,
          mean / instr, ms * 1e6 / (instr * waves_per_simd));
+  hipEventDestroy(e0); hipEventDestroy(e1);
   hipFree(out); hipFree(cyc);
 }
 int main() {
-  for (int w : {1, 2, 4, 8}) {
+  for (int w : {1, 2, 4, 6, 8}) {
     run<0>("scalar fma, 8 independent", w);
     run<1>("scalar fma, dependent", w);
     run<5>("scalar fma, 2 dependent chains", w);
     run<2>("packed fma, 4 independent", w);
     run<3>("packed fma, dependent", w);
     run<4>("packed mul, 4 independent", w);
+    run<6>("v_cmp + s_nop 1 + v_cndmask (per pair)", w);
+    run<13>("v_cmp + 2 VALU + v_cndmask (per group of 4)", w);
+    run<7>("v_med3_f32 (0, SGPR)", w);
+    run<8>("v_max_f32, SGPR operand", w);
+    run<9>("v_mov_b32 from SGPR", w);
+    run<10>("s_nop 1", w);
+    run<11>("v_rsq_f32, 8 independent", w);
+    run<12>("v_fma_f64, 4 independent", w);
   }
   return 0;
 }
