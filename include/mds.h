@@ -534,6 +534,44 @@ int mds_dlqr_compute(mds_handle* h, const void* obs_dev, const void* des_dev, vo
  * [n,20] or NULL. */
 int mds_rollout_dlqr_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_last_dev, void* stream);
 
+/* ---- FedCE and the decentralised LQR on the 9-state thrust / body-rate model (control/dlqr/decentralized_lqr_omega.py,
+ * simulations/EnvGeometricOmega.py fedCE) ----
+ * x = obs_to_lin_model(obs, 9) = [rpy, vel, pos], u = (thrust, body rates).  Per drone the handle keeps, in float64 in every dtype,
+ * the full theta = [A^T; B^T] [13,9] (never projected), the information matrix V [13,13] that theta_update2 calls P (:115,
+ * V <- V + phi phi^T) and its inverse, carried by Sherman-Morrison.  The low level is the handle's ThrustOmega PID memory
+ * (mds_lowlevel_reset): it lives across these calls as it lives in the reference's DecentralizedLQROmega object.  The same
+ * restrictions and conventions (alignment, status codes, enqueue-only calls) as the 12-state entry points above. */
+/* DecentralizedLQROmega's restrictions are mds_fedce_supported's (:13-70 builds nothing more). */
+int mds_fedce_omega_supported(const mds_config* cfg);
+/* V0 [169] (row-major 13 x 13; the reference starts at I, :62) and theta0 [117] (13 x 9 = hstack([Ahat, Bhat]).T, :59) to every
+ * drone.  MDS_EINVAL if V0 is singular.  Synchronous. */
+int mds_fedce_omega_init(mds_handle* h, const double V0[169], const double theta0[117]);
+/* Host copies (get_thetai :72-78, P :62): theta_host [n,13,9], V_host [n,13,13]; either may be NULL.  Synchronous.  set inverts
+ * every V on the host (overwrite_theta :80-85 for theta). */
+int mds_fedce_omega_get(mds_handle* h, double* theta_host, double* V_host);
+int mds_fedce_omega_set(mds_handle* h, const double* theta_host, const double* V_host);
+/* One warm-up (EnvGeometricOmega.py:143-193) or exploration phase (:226-262) of fedCE_iteration, n_steps steps in one launch.  Per step
+ * and drone: e_t = error_state(x_t, x_des) (:174-183), action = compute_low_level(u, obs) (:238-249), phi = [e_t, max(u0, 0) - M G,
+ * u1..3], env.step with the handle's wind, e_{t+1} and theta_update2 (:110-123; its forward_predict :87-97 is solve_ivp's RK45
+ * restated) -- update 0: never; 1: every step; 2: every step but this call's first (the reference's `if i != 0` for a call that
+ * covers a whole phase).  u_dev [n_steps, n, 4] float64 raw inputs; xdes_dev [n,9] float64 ([rpy, vel, pos] of x_des; NULL = zeros);
+ * obs_log_dev [n_steps, n, 20] (storage type), theta_log_dev [n_steps, n, 13, 9] float64 (theta after the step) and status_dev [n]
+ * int32 may be NULL.  A drone whose forward prediction does not finish (bit 0: the attempt cap, bit 1: a non-finite norm, bit 2: step
+ * below 10 ulp) skips that update and has the bits or-ed into status_dev.  obs_dev [n,20]: the last observation (or NULL). */
+int mds_fedce_omega_identify(mds_handle* h, int n_steps, const double* u_dev, const double* xdes_dev, int update, void* obs_log_dev,
+                             double* theta_log_dev, int32_t* status_dev, void* obs_dev, void* stream);
+/* The gain of every env (compute_controller :185-204): K_host [E, 4D, 9D] float64, uploaded in the env's dtype to the device layout
+ * [E][4][9D][D] (element (env, q, col, j) = K_env[4j + q][col]).  Synchronous. */
+int mds_set_dlqr_omega_gain(mds_handle* h, const double* K_host);
+/* DecentralizedLQROmega.compute(obs, skip_low_level) (:212-231) for every env: obs_dev [n,20], des_dev [n,11] (pos, vel, -, yaw, -)
+ * -> u_dev [n,4] = cap_u(-K e + (M G, 0, 0, 0)) and action_dev [n,4] = compute_low_level(uncapped u, obs), which advances the PID
+ * memory.  action_dev NULL is skip_low_level: the PID memory is not advanced.  u_dev may be NULL. */
+int mds_dlqr_omega_compute(mds_handle* h, const void* obs_dev, const void* des_dev, void* u_dev, void* action_dev, void* stream);
+/* n_steps control steps of the 9-state dLQR loop (fedCE_iteration's CE phase :199-223, do_control with 'dlqr' :297-329: trajectory table
+ * -> error state -> coupled -K e -> ThrustOmega low level -> env.step with wind) in one launch; the PID memory goes handle ->
+ * registers -> handle.  obs_log_dev [n_steps, n, 20] or NULL, obs_last_dev [n,20] or NULL. */
+int mds_rollout_dlqr_omega_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_last_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,14 @@ PROTOTYPES = {
     "mds_set_dlqr_gain": (C.c_int, [_P, _PD]),
     "mds_dlqr_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "mds_rollout_dlqr_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
+    "mds_fedce_omega_supported": (C.c_int, [C.POINTER(MdsConfig)]),
+    "mds_fedce_omega_init": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_omega_get": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_omega_set": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_omega_identify": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "mds_set_dlqr_omega_gain": (C.c_int, [_P, _PD]),
+    "mds_dlqr_omega_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "mds_rollout_dlqr_omega_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@ from .lqr.lqr_omega_controller import LQROmegaController  # noqa: F401
 from .lqr.lqr_YO_controller import LQRYankOmegaController  # noqa: F401
 from .lqr.lqr_controller import LQRController  # noqa: F401
 from .dlqr.decentralized_lqr import DecentralizedLQR  # noqa: F401
+from .dlqr.decentralized_lqr_omega import DecentralizedLQROmega  # noqa: F401
 
 
 class CrazyflieLQR:

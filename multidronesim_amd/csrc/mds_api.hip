@@ -20,6 +20,7 @@
 #if MDS_PART & 2
 #include "mds_cbf_kernels.hip"      // (part 2 only: it defines a non-template kernel)
 #include "mds_fedce_kernels.hip"    // FedCE identification and the dLQR kernels (part 2 only)
+#include "mds_fedce_omega_kernels.hip"   // the same on the 9-state thrust / body-rate model (part 2 only)
 #else
 #include "mds_cbf.hpp"
 #endif
@@ -167,6 +168,11 @@ struct mds_handle {
   double* fedce_P = nullptr;      // [n][16][16]
   double* fedce_theta = nullptr;  // [n][12]: the free entries of theta (mds_fedce_kernels.hip)
   void* dlqr_K = nullptr;         // T [E][4][12 D][D] (dlqr_kidx)
+  // the 9-state learner (mds_fedce_omega_*, mds_*dlqr_omega*): information matrix V, W = V^-1 and the full theta, float64
+  double* fo_V = nullptr;         // [n][13][13]
+  double* fo_W = nullptr;         // [n][13][13]
+  double* fo_theta = nullptr;     // [n][13][9]
+  void* dlqr_omega_K = nullptr;   // T [E][4][9 D][D] (dlqr_kidx_m<9>)
   bool track_rpm = false;        // last_rpm planes maintained by every step kernel (DYN_DRAG, order-3 CBF, or cfg.track_last_rpm)
   bool rpm_stale = false;        // a step ran without tracking since the last reset
 };
@@ -527,6 +533,10 @@ int mds_destroy(mds_handle* h) {
   if (h->fedce_P) (void)hipFree(h->fedce_P);
   if (h->fedce_theta) (void)hipFree(h->fedce_theta);
   if (h->dlqr_K) (void)hipFree(h->dlqr_K);
+  if (h->fo_V) (void)hipFree(h->fo_V);
+  if (h->fo_W) (void)hipFree(h->fo_W);
+  if (h->fo_theta) (void)hipFree(h->fo_theta);
+  if (h->dlqr_omega_K) (void)hipFree(h->dlqr_omega_K);
   if (h->split_st) (void)hipStreamDestroy(h->split_st);
   for (int k = 0; k < 2; ++k)
     if (h->split_ev[k]) (void)hipEventDestroy(h->split_ev[k]);
@@ -2371,6 +2381,212 @@ int mds_rollout_dlqr_fused(mds_handle* h, double t0, int n_steps, void* obs_log,
       k_dlqr_rollout<T, T, DRAG()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, (const T*)h->dlqr_K, E, D, h->ld, t0, dt, n_steps, h->traj_mode,
                                                                  (T*)h->state, (const T*)h->origin, (const T*)h->lem, SegTable{h->segs, h->nseg_total},
                                                                  h->tinfo, (T*)rpm_track(h), (T*)obs_log, (T*)obs_last);
+    }, has_drag(h));
+  });
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// FedCE and the decentralised LQR on the 9-state thrust / body-rate model (mds_fedce_omega_kernels.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+int mds_fedce_omega_supported(const mds_config* cfg) {
+  if (!cfg) return fail(MDS_EINVAL, "mds_fedce_omega_supported: null config");
+  return mds_fedce_supported(cfg);
+}
+
+// W = V^-1 [13,13] by Gauss-Jordan with partial pivoting (host, float64); false if V is singular
+static bool fo_invert(const double* V, double* W) {
+  constexpr int R = kOmegaR;
+  double a[R][2 * R];
+  for (int r = 0; r < R; ++r)
+    for (int k = 0; k < R; ++k) {
+      a[r][k] = V[r * R + k];
+      a[r][R + k] = r == k ? 1.0 : 0.0;
+    }
+  for (int p = 0; p < R; ++p) {
+    int best = p;
+    for (int r = p + 1; r < R; ++r)
+      if (fabs(a[r][p]) > fabs(a[best][p])) best = r;
+    if (!(fabs(a[best][p]) > 0.0)) return false;
+    if (best != p)
+      for (int k = 0; k < 2 * R; ++k) std::swap(a[p][k], a[best][k]);
+    const double d = a[p][p];
+    for (int k = 0; k < 2 * R; ++k) a[p][k] /= d;
+    for (int r = 0; r < R; ++r) {
+      if (r == p) continue;
+      const double m = a[r][p];
+      for (int k = 0; k < 2 * R; ++k) a[r][k] -= m * a[p][k];
+    }
+  }
+  for (int r = 0; r < R; ++r)
+    for (int k = 0; k < R; ++k) W[r * R + k] = a[r][R + k];
+  return true;
+}
+
+static int fo_ready(mds_handle* h) {
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fo_V) {             // all three or none: fo_V alone says "initialised" to the other entry points
+    double* buf[3] = {nullptr, nullptr, nullptr};
+    const size_t bytes[3] = {(size_t)h->n * kOmegaR * kOmegaR * sizeof(double), (size_t)h->n * kOmegaR * kOmegaR * sizeof(double),
+                             (size_t)h->n * kOmegaR * kOmegaM * sizeof(double)};
+    for (int k = 0; k < 3; ++k)
+      if (hipMalloc(&buf[k], bytes[k]) != hipSuccess) {
+        for (int j = 0; j < k; ++j) (void)hipFree(buf[j]);
+        return fail(MDS_ENOMEM, "mds_fedce_omega_init: hipMalloc of the learner state failed");
+      }
+    h->fo_V = buf[0]; h->fo_W = buf[1]; h->fo_theta = buf[2];
+  }
+  return MDS_OK;
+}
+
+int mds_fedce_omega_init(mds_handle* h, const double V0[169], const double theta0[117]) {
+  MDS_DEV(h);
+  if (!h || !V0 || !theta0) return fail(MDS_EINVAL, "mds_fedce_omega_init: null argument");
+  if (int rc = fo_ready(h)) return rc;
+  constexpr size_t RR = kOmegaR * kOmegaR, RM = kOmegaR * kOmegaM;
+  double W0[RR];
+  if (!fo_invert(V0, W0)) return fail(MDS_EINVAL, "mds_fedce_omega_init: V0 is singular");
+  std::vector<double> V((size_t)h->n * RR), W((size_t)h->n * RR), th((size_t)h->n * RM);
+  for (size_t i = 0; i < (size_t)h->n; ++i) {
+    memcpy(&V[i * RR], V0, RR * sizeof(double));
+    memcpy(&W[i * RR], W0, RR * sizeof(double));
+    memcpy(&th[i * RM], theta0, RM * sizeof(double));
+  }
+  MDS_HIP(hipDeviceSynchronize());
+  MDS_HIP(hipMemcpy(h->fo_V, V.data(), V.size() * sizeof(double), hipMemcpyHostToDevice));
+  MDS_HIP(hipMemcpy(h->fo_W, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice));
+  MDS_HIP(hipMemcpy(h->fo_theta, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice));
+  return MDS_OK;
+}
+
+int mds_fedce_omega_get(mds_handle* h, double* theta_host, double* V_host) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_fedce_omega_get: null handle");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fo_V) return fail(MDS_ESTATE, "mds_fedce_omega_get: call mds_fedce_omega_init first");
+  MDS_HIP(hipDeviceSynchronize());
+  if (V_host) MDS_HIP(hipMemcpy(V_host, h->fo_V, (size_t)h->n * kOmegaR * kOmegaR * sizeof(double), hipMemcpyDeviceToHost));
+  if (theta_host) MDS_HIP(hipMemcpy(theta_host, h->fo_theta, (size_t)h->n * kOmegaR * kOmegaM * sizeof(double), hipMemcpyDeviceToHost));
+  return MDS_OK;
+}
+
+int mds_fedce_omega_set(mds_handle* h, const double* theta_host, const double* V_host) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_fedce_omega_set: null handle");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fo_V) return fail(MDS_ESTATE, "mds_fedce_omega_set: call mds_fedce_omega_init first");
+  constexpr size_t RR = kOmegaR * kOmegaR;
+  std::vector<double> W;
+  if (V_host) {
+    W.resize((size_t)h->n * RR);
+    for (size_t i = 0; i < (size_t)h->n; ++i)
+      if (!fo_invert(V_host + i * RR, &W[i * RR])) return fail(MDS_EINVAL, "mds_fedce_omega_set: a V is singular");
+  }
+  MDS_HIP(hipDeviceSynchronize());
+  if (V_host) {
+    MDS_HIP(hipMemcpy(h->fo_V, V_host, W.size() * sizeof(double), hipMemcpyHostToDevice));
+    MDS_HIP(hipMemcpy(h->fo_W, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (theta_host) MDS_HIP(hipMemcpy(h->fo_theta, theta_host, (size_t)h->n * kOmegaR * kOmegaM * sizeof(double), hipMemcpyHostToDevice));
+  return MDS_OK;
+}
+
+int mds_fedce_omega_identify(mds_handle* h, int n_steps, const double* u_dev, const double* xdes_dev, int update, void* obs_log_dev,
+                             double* theta_log_dev, int32_t* status_dev, void* obs_dev, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_fedce_omega_identify: null handle");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (n_steps < 0 || (n_steps > 0 && !u_dev) || update < 0 || update > 2) return fail(MDS_EINVAL, "mds_fedce_omega_identify: n_steps / u_dev / update");
+  if (!h->fo_V) return fail(MDS_ESTATE, "mds_fedce_omega_identify: call mds_fedce_omega_init first");
+  if (!aligned16(obs_log_dev) || !aligned16(obs_dev) || !aligned16(theta_log_dev) || !aligned16(status_dev) || !aligned16(u_dev) ||
+      !aligned16(xdes_dev))
+    return fail(MDS_EALIGN, "mds_fedce_omega_identify: u / xdes / log / status / obs buffers");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_steps > 0) {
+    const dim3 grid = grid_for(h->n * 16, kFedceBlock);
+    with_dtype_no_half(h->cfg.dtype, [&](auto DT) {         // f32 / f64 (mds_fedce_supported)
+      using T = typename decltype(DT)::T;
+      with_flags([&](auto DRAG) {
+        k_fedce_omega_identify<T, T, DRAG()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, h->cfg.M * h->cfg.G, 1.0 / h->cfg.ctrl_freq, h->n, h->ld, n_steps,
+                                                                           (T*)h->state, (const T*)h->origin, (T*)rpm_track(h), (T*)h->ll, u_dev, xdes_dev,
+                                                                           update, h->fo_V, h->fo_W, h->fo_theta, (T*)obs_log_dev, theta_log_dev, status_dev);
+      }, has_drag(h));
+    });
+    MDS_HIP(hipGetLastError());
+  }
+  if (obs_dev) {
+    if (obs_log_dev && n_steps > 0) {
+      const size_t obs_bytes = (size_t)h->n * kObsDim * elem_size(h->cfg.dtype);
+      MDS_HIP(hipMemcpyAsync(obs_dev, (char*)obs_log_dev + (size_t)(n_steps - 1) * obs_bytes, obs_bytes, hipMemcpyDeviceToDevice, st));
+    } else {
+      return mds_get_obs(h, obs_dev, stream);
+    }
+  }
+  return MDS_OK;
+}
+
+int mds_set_dlqr_omega_gain(mds_handle* h, const double* K_host) {
+  MDS_DEV(h);
+  if (!h || !K_host) return fail(MDS_EINVAL, "mds_set_dlqr_omega_gain: null argument");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones;
+  const size_t per = (size_t)4 * kOmegaM * D * D, total = per * E;
+  const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
+  if (!h->dlqr_omega_K) MDS_HIP(hipMalloc(&h->dlqr_omega_K, total * es));
+  std::vector<double> kd(h->cfg.dtype == MDS_F64 ? total : 0);
+  std::vector<float> kf(h->cfg.dtype == MDS_F64 ? 0 : total);
+  for (size_t e = 0; e < (size_t)E; ++e)
+    for (int j = 0; j < D; ++j)
+      for (int q = 0; q < 4; ++q)
+        for (int col = 0; col < kOmegaM * D; ++col) {
+          const double v = K_host[e * per + (size_t)(4 * j + q) * (kOmegaM * D) + col];
+          const size_t at = dlqr_kidx_m<kOmegaM>(e, D, j, q, col);
+          if (kd.size()) kd[at] = v;
+          else kf[at] = (float)v;
+        }
+  MDS_HIP(hipDeviceSynchronize());
+  MDS_HIP(hipMemcpy(h->dlqr_omega_K, kd.size() ? (const void*)kd.data() : (const void*)kf.data(), total * es, hipMemcpyHostToDevice));
+  return MDS_OK;
+}
+
+int mds_dlqr_omega_compute(mds_handle* h, const void* obs, const void* des, void* u, void* action, void* stream) {
+  MDS_DEV(h);
+  if (!h || !obs || !des || (!u && !action)) return fail(MDS_EINVAL, "mds_dlqr_omega_compute: null argument");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->dlqr_omega_K) return fail(MDS_ESTATE, "mds_dlqr_omega_compute: call mds_set_dlqr_omega_gain first");
+  if (!aligned16(u) || !aligned16(action)) return fail(MDS_EALIGN, "mds_dlqr_omega_compute: u_dev/action_dev");
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones, epb = kFedceBlock / D;
+  const dim3 grid((unsigned)((E + epb - 1) / epb));
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {           // f32 / f64 (mds_fedce_supported)
+    using T = typename decltype(DT)::T;
+    k_dlqr_omega_compute<T, T><<<grid, kFedceBlock, 0, (hipStream_t)stream>>>(params<T>(h).c, (const T*)h->dlqr_omega_K, E, D, h->ld,
+                                                                              (T)(1.0 / h->cfg.ctrl_freq), (T*)h->ll, (const T*)obs, (const T*)des,
+                                                                              (T*)u, (T*)action);
+  });
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+
+int mds_rollout_dlqr_omega_fused(mds_handle* h, double t0, int n_steps, void* obs_log, void* obs_last, void* stream) {
+  MDS_DEV(h);
+  if (!h || n_steps < 0) return fail(MDS_EINVAL, "mds_rollout_dlqr_omega_fused: null handle / n_steps");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->has_traj) return fail(MDS_ESTATE, "mds_rollout_dlqr_omega_fused: call mds_set_lemniscate / mds_set_trajectory_segments first");
+  if (!h->dlqr_omega_K) return fail(MDS_ESTATE, "mds_rollout_dlqr_omega_fused: call mds_set_dlqr_omega_gain first");
+  if (!aligned16(obs_log) || !aligned16(obs_last)) return fail(MDS_EALIGN, "mds_rollout_dlqr_omega_fused: obs buffers");
+  if (n_steps == 0) return MDS_OK;
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones, epb = kFedceBlock / D;
+  const dim3 grid((unsigned)((E + epb - 1) / epb));
+  const double dt = 1.0 / h->cfg.ctrl_freq;
+  hipStream_t st = (hipStream_t)stream;
+  with_dtype_no_half(h->cfg.dtype, [&](auto DT) {           // f32 / f64 (mds_fedce_supported)
+    using T = typename decltype(DT)::T;
+    with_flags([&](auto DRAG) {
+      k_dlqr_omega_rollout<T, T, DRAG()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, (const T*)h->dlqr_omega_K, E, D, h->ld, t0, dt, n_steps,
+                                                                       h->traj_mode, (T*)h->state, (const T*)h->origin, (const T*)h->lem,
+                                                                       SegTable{h->segs, h->nseg_total}, h->tinfo, (T*)rpm_track(h), (T*)h->ll,
+                                                                       (T*)obs_log, (T*)obs_last);
     }, has_drag(h));
   });
   MDS_HIP(hipGetLastError());
