@@ -572,6 +572,31 @@ int mds_dlqr_omega_compute(mds_handle* h, const void* obs_dev, const void* des_d
  * registers -> handle.  obs_log_dev [n_steps, n, 20] or NULL, obs_last_dev [n,20] or NULL. */
 int mds_rollout_dlqr_omega_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_last_dev, void* stream);
 
+/* ---- The dLQR gains on the device (compute_controller of both models: K = R^-1 B^T P, P the stabilising solution of the continuous
+ * Riccati equation A^T P + P A - P B R^-1 B^T P + Q = 0 on each env's identified model) ----
+ * A and B are read from the handle's learner state (mds_fedce_init / mds_fedce_omega_init first: MDS_ESTATE otherwise), Q_host
+ * [M D, M D] and R_host [4D, 4D] (row-major float64, M = 12 or 9) are read before the call returns.  R must be block diagonal in 4 x 4
+ * blocks (MDS_EUNSUPPORTED otherwise; MDS_EINVAL for a singular block or a Q that is not symmetric).  The solution is block diagonal
+ * over the connected components of Q's M x M block graph, and each component of each env is one problem for one wavefront: single
+ * drones of either model and pairs of the 12-state model (DecentralizedLQR's xy coupling of drones 0 and 1).  A component of more
+ * than two drones, or a coupled pair of the 9-state model, is MDS_EUNSUPPORTED with mds_last_error naming its drones; nothing is
+ * touched then.  force_diagonal needs no flag: pass kron(I, ind_Q).  Float64 throughout: the matrix sign function of the Hamiltonian
+ * by the determinant-scaled Newton iteration, at most max_iter iterations (<= 0: 32).
+ * status_dev [E] int32 (out): 0, or the bits of the env's failed problems -- 1: the iteration cap was reached, 2: a zero or non-finite
+ * pivot or a non-finite result (an unstabilisable model ends here), 4: the relative residual is above 1e-11.  An env with status 0
+ * gets its gain written into the buffer mds_dlqr_compute / mds_rollout_dlqr_fused read, in the layout and dtype of
+ * mds_set_dlqr_gain; an env with a bit set keeps its previous gain entirely (zeros before the first).  K_dev: NULL, or [E, 4D, M D]
+ * float64 (out): the same gains as mds_set_dlqr_gain takes them, zeros for an env with a bit set.  iters_dev: NULL, or [E] int32 (out):
+ * the most iterations any of the env's problems took.  Device buffers 16-byte aligned (MDS_EALIGN).  The call only enqueues on
+ * `stream`, except that the first call and a call whose Q or R differ from the previous call's synchronise the device once to
+ * upload the group table. */
+int mds_dlqr_solve_gain(mds_handle* h, const double* Q_host, const double* R_host, int max_iter, double* K_dev, int32_t* status_dev,
+                        int32_t* iters_dev, void* stream);
+/* The same for the 9-state model: theta of mds_fedce_omega_*, Q_host [9D, 9D], K_dev [E, 4D, 9D], the gain buffer of
+ * mds_set_dlqr_omega_gain. */
+int mds_dlqr_omega_solve_gain(mds_handle* h, const double* Q_host, const double* R_host, int max_iter, double* K_dev, int32_t* status_dev,
+                              int32_t* iters_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

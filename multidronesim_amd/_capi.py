@@ -141,6 +141,8 @@ PROTOTYPES = {
     "mds_set_dlqr_omega_gain": (C.c_int, [_P, _PD]),
     "mds_dlqr_omega_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "mds_rollout_dlqr_omega_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
+    "mds_dlqr_solve_gain": (C.c_int, [_P, _PD, _PD, C.c_int, _P, _P, _P, _P]),
+    "mds_dlqr_omega_solve_gain": (C.c_int, [_P, _PD, _PD, C.c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -3,8 +3,9 @@ whose models FedCE (simulations/EnvGeometric.py fedCE) identifies on line by rec
 
 The per-drone RLS state (P [16,16] and theta, float64 in every env dtype) lives on the device: ``identify`` runs a whole warm-up or
 exploration phase of fedCE_iteration per launch (mds_fedce_identify) and ``rollout`` the CE phase / do_control loop
-(mds_rollout_dlqr_fused).  The Riccati solve stays on the host in float64 (scipy, once per FedCE iteration, as
-control/lqr/lqr_controller.py does) and its gain is uploaded per env (mds_set_dlqr_gain).
+(mds_rollout_dlqr_fused).  The Riccati solve runs once per FedCE iteration in float64: on the host by default (scipy, one env after
+the other, as control/lqr/lqr_controller.py does; the gain is uploaded per env with mds_set_dlqr_gain), or for every env at once on
+the device with ``compute_controller(solver="device")`` (mds_dlqr_solve_gain, which writes the gains where the kernels read them).
 
 Arrays gain a leading env axis when ``env.NUM_ENVS > 1``: theta [E, 16D, 12D], P [E, D, 16, 16], K [E, 4D, 12D]."""
 from __future__ import annotations
@@ -203,10 +204,31 @@ class DecentralizedLQR(BaseController):
                 self.pred_errors[i + D].append(self._one(perr[t, :, i, 1]))
                 self.pred_thetas[i].append(self._one(th[t, :, i]))
 
-    def compute_controller(self, force_diagonal=False):
-        """K from the continuous ARE on the identified model (:300-317), every env on the host in float64, then uploaded.  One env: an
-        ARE failure raises as in the reference.  Several: that env keeps its previous K (zeros before the first) and are_status[e] is False."""
+    def _are_gain(self, A, B, force_diagonal):
+        """K [4D, 12D] of one env's model on the host (scipy); raises what solve_continuous_are raises."""
+        D = self.num_robots
+        if not force_diagonal:
+            P = la.solve_continuous_are(A, B, self.Q, self.R, e=None, s=None, balanced=True)
+            return la.solve(self.R, B.T @ P)
+        K = np.zeros((4 * D, 12 * D))
+        for i in range(D):
+            Ai = A[12 * i:12 * (i + 1), 12 * i:12 * (i + 1)]
+            Bi = B[12 * i:12 * (i + 1), 4 * i:4 * (i + 1)]
+            Pi = la.solve_continuous_are(Ai, Bi, self.ind_Q, self.ind_R, e=None, s=None, balanced=True)
+            K[4 * i:4 * (i + 1), 12 * i:12 * (i + 1)] = la.solve(self.ind_R, Bi.T @ Pi)   # (the reference's R is 4D x 4D here)
+        return K
+
+    def compute_controller(self, force_diagonal=False, solver="host", host_fallback=True):
+        """K from the continuous ARE on the identified model (:300-317) in float64.  ``solver="host"``: every env on the host (scipy),
+        then uploaded.  One env: an ARE failure raises as in the reference.  Several: that env keeps its previous K (zeros before the
+        first) and are_status[e] is False.  ``solver="device"``: every env at once on the device (mds_dlqr_solve_gain); care_status [E]
+        keeps its status bits and care_iters [E] its iteration counts.  An env it flags is solved again on the host when
+        ``host_fallback`` is set; one that stays unsolved is treated as above (one env: np.linalg.LinAlgError)."""
         D, E = self.num_robots, self.num_envs
+        if solver == "device":
+            return self._compute_controller_device(force_diagonal, host_fallback)
+        if solver != "host":
+            raise ValueError(f"solver must be 'host' or 'device', not {solver!r}")
         th = self._stack(self._get()[0])                            # [E, 16D, 12D]
         Kprev = None if self.K is None else np.broadcast_to(self.K, (E, 4 * D, 12 * D))
         K = np.zeros((E, 4 * D, 12 * D))
@@ -215,15 +237,7 @@ class DecentralizedLQR(BaseController):
             A = th[e, :12 * D, :].T
             B = th[e, 12 * D:, :].T
             try:
-                if force_diagonal:
-                    for i in range(D):
-                        Ai = A[12 * i:12 * (i + 1), 12 * i:12 * (i + 1)]
-                        Bi = B[12 * i:12 * (i + 1), 4 * i:4 * (i + 1)]
-                        Pi = la.solve_continuous_are(Ai, Bi, self.ind_Q, self.ind_R, e=None, s=None, balanced=True)
-                        K[e, 4 * i:4 * (i + 1), 12 * i:12 * (i + 1)] = la.solve(self.ind_R, Bi.T @ Pi)   # (the reference's R is 4D x 4D here)
-                else:
-                    P = la.solve_continuous_are(A, B, self.Q, self.R, e=None, s=None, balanced=True)
-                    K[e] = la.solve(self.R, B.T @ P)
+                K[e] = self._are_gain(A, B, force_diagonal)
             except (np.linalg.LinAlgError, ValueError):
                 if E == 1:
                     raise
@@ -232,6 +246,38 @@ class DecentralizedLQR(BaseController):
         self.are_status = status
         self.K = self._one(K)
         self.upload_gain(K)
+
+    def _compute_controller_device(self, force_diagonal, host_fallback):
+        env, D, E = self.env, self.num_robots, self.num_envs
+        Q = np.ascontiguousarray(np.kron(np.eye(D), self.ind_Q) if force_diagonal else self.Q, dtype=np.float64)
+        R = np.ascontiguousarray(self.R, dtype=np.float64)
+        K_dev = torch.empty((E, 4 * D, 12 * D), dtype=torch.float64, device=env.device)
+        st_dev = torch.empty(E, dtype=torch.int32, device=env.device)
+        it_dev = torch.empty(E, dtype=torch.int32, device=env.device)
+        capi.check(env._lib.mds_dlqr_solve_gain(env._h, capi.as_double_ptr(Q), capi.as_double_ptr(R), C.c_int(0), C.c_void_p(K_dev.data_ptr()),
+                                                C.c_void_p(st_dev.data_ptr()), C.c_void_p(it_dev.data_ptr()), C.c_void_p(stream_ptr(env.device))),
+                   "mds_dlqr_solve_gain")
+        K = K_dev.cpu().numpy()
+        self.care_status, self.care_iters = st_dev.cpu().numpy(), it_dev.cpu().numpy()
+        status = self.care_status == 0
+        Kprev = None if self.K is None else np.broadcast_to(self.K, (E, 4 * D, 12 * D))
+        flagged = np.flatnonzero(~status)
+        th = self._stack(self._get()[0]) if (host_fallback and len(flagged)) else None
+        resolved = False
+        for e in flagged:
+            try:
+                if not host_fallback:
+                    raise np.linalg.LinAlgError(f"mds_dlqr_solve_gain: env {e} ended with status {self.care_status[e]}")
+                K[e] = self._are_gain(th[e, :12 * D, :].T, th[e, 12 * D:, :].T, force_diagonal)
+                status[e] = resolved = True
+            except (np.linalg.LinAlgError, ValueError):
+                if E == 1:
+                    raise
+                K[e] = Kprev[e] if Kprev is not None else 0.0
+        self.are_status = status
+        self.K = self._one(K)
+        if resolved:                                                # the device already holds every other env's gain
+            self.upload_gain(K)
 
     def upload_gain(self, K):
         """K [4D,12D] (every env) or [E,4D,12D] -> the device (mds_set_dlqr_gain).  The layout the kernels read is documented in

@@ -5,8 +5,9 @@ whose innovation is taken against a forward prediction (scipy's solve_ivp in the
 
 The per-drone learner state (theta [13,9], the information matrix the reference calls P [13,13] and its inverse, float64 in every
 env dtype) and the ThrustOmega PID memory live on the device: ``identify`` runs a whole warm-up or exploration phase per launch
-(mds_fedce_omega_identify) and ``rollout`` the CE phase / do_control loop (mds_rollout_dlqr_omega_fused).  The Riccati solve stays on
-the host in float64 (scipy) and its gain is uploaded per env (mds_set_dlqr_omega_gain).
+(mds_fedce_omega_identify) and ``rollout`` the CE phase / do_control loop (mds_rollout_dlqr_omega_fused).  The Riccati solve runs in
+float64 on the host by default (scipy; the gain is uploaded per env with mds_set_dlqr_omega_gain) or, with
+``compute_controller(solver="device")``, for every env at once on the device (mds_dlqr_omega_solve_gain).
 
 Arrays gain a leading env axis when ``env.NUM_ENVS > 1``: theta [E, 13D, 9D], P [E, D, 13, 13], K [E, 4D, 9D]."""
 from __future__ import annotations
@@ -166,10 +167,31 @@ class DecentralizedLQROmega(BaseController):
         self.status = self._status_dev.cpu().numpy()
         return obs_log, env._obs, thl
 
-    def compute_controller(self, force_diagonal=False):
-        """K from the continuous ARE on the identified model (:185-204), every env on the host in float64, then uploaded.  One env: an
-        ARE failure raises as in the reference.  Several: that env keeps its previous K (zeros before the first) and are_status[e] is False."""
+    def _are_gain(self, A, B, force_diagonal):
+        """K [4D, 9D] of one env's model on the host (scipy); raises what solve_continuous_are raises."""
+        D, m, n = self.num_robots, self.m, self.n
+        if not force_diagonal:
+            P = la.solve_continuous_are(A, B, self.Q, self.R, e=None, s=None, balanced=True)
+            return la.solve(self.R, B.T @ P)
+        K = np.zeros((n * D, m * D))
+        for i in range(D):
+            Ai = A[m * i:m * (i + 1), m * i:m * (i + 1)]
+            Bi = B[m * i:m * (i + 1), n * i:n * (i + 1)]
+            Pi = la.solve_continuous_are(Ai, Bi, self.ind_Q, self.ind_R, e=None, s=None, balanced=True)
+            K[n * i:n * (i + 1), m * i:m * (i + 1)] = la.solve(self.ind_R, Bi.T @ Pi)   # (the reference's R is 4D x 4D here)
+        return K
+
+    def compute_controller(self, force_diagonal=False, solver="host", host_fallback=True):
+        """K from the continuous ARE on the identified model (:185-204) in float64.  ``solver="host"``: every env on the host (scipy),
+        then uploaded.  One env: an ARE failure raises as in the reference.  Several: that env keeps its previous K (zeros before the
+        first) and are_status[e] is False.  ``solver="device"``: every env at once on the device (mds_dlqr_omega_solve_gain);
+        care_status [E] keeps its status bits and care_iters [E] its iteration counts.  An env it flags is solved again on the host when
+        ``host_fallback`` is set; one that stays unsolved is treated as above (one env: np.linalg.LinAlgError)."""
         D, E, m, n = self.num_robots, self.num_envs, self.m, self.n
+        if solver == "device":
+            return self._compute_controller_device(force_diagonal, host_fallback)
+        if solver != "host":
+            raise ValueError(f"solver must be 'host' or 'device', not {solver!r}")
         th = self._stack(self._get()[0])                            # [E, 13D, 9D]
         Kprev = None if self.K is None else np.broadcast_to(self.K, (E, n * D, m * D))
         K = np.zeros((E, n * D, m * D))
@@ -178,15 +200,7 @@ class DecentralizedLQROmega(BaseController):
             A = th[e, :m * D, :].T
             B = th[e, m * D:, :].T
             try:
-                if force_diagonal:
-                    for i in range(D):
-                        Ai = A[m * i:m * (i + 1), m * i:m * (i + 1)]
-                        Bi = B[m * i:m * (i + 1), n * i:n * (i + 1)]
-                        Pi = la.solve_continuous_are(Ai, Bi, self.ind_Q, self.ind_R, e=None, s=None, balanced=True)
-                        K[e, n * i:n * (i + 1), m * i:m * (i + 1)] = la.solve(self.ind_R, Bi.T @ Pi)   # (the reference's R is 4D x 4D here)
-                else:
-                    P = la.solve_continuous_are(A, B, self.Q, self.R, e=None, s=None, balanced=True)
-                    K[e] = la.solve(self.R, B.T @ P)
+                K[e] = self._are_gain(A, B, force_diagonal)
             except (np.linalg.LinAlgError, ValueError):
                 if E == 1:
                     raise
@@ -195,6 +209,38 @@ class DecentralizedLQROmega(BaseController):
         self.are_status = status
         self.K = self._one(K)
         self.upload_gain(K)
+
+    def _compute_controller_device(self, force_diagonal, host_fallback):
+        env, D, E, m, n = self.env, self.num_robots, self.num_envs, self.m, self.n
+        Q = np.ascontiguousarray(np.kron(np.eye(D), self.ind_Q) if force_diagonal else self.Q, dtype=np.float64)
+        R = np.ascontiguousarray(self.R, dtype=np.float64)
+        K_dev = torch.empty((E, n * D, m * D), dtype=torch.float64, device=env.device)
+        st_dev = torch.empty(E, dtype=torch.int32, device=env.device)
+        it_dev = torch.empty(E, dtype=torch.int32, device=env.device)
+        capi.check(env._lib.mds_dlqr_omega_solve_gain(env._h, capi.as_double_ptr(Q), capi.as_double_ptr(R), C.c_int(0),
+                                                      C.c_void_p(K_dev.data_ptr()), C.c_void_p(st_dev.data_ptr()), C.c_void_p(it_dev.data_ptr()),
+                                                      C.c_void_p(stream_ptr(env.device))), "mds_dlqr_omega_solve_gain")
+        K = K_dev.cpu().numpy()
+        self.care_status, self.care_iters = st_dev.cpu().numpy(), it_dev.cpu().numpy()
+        status = self.care_status == 0
+        Kprev = None if self.K is None else np.broadcast_to(self.K, (E, n * D, m * D))
+        flagged = np.flatnonzero(~status)
+        th = self._stack(self._get()[0]) if (host_fallback and len(flagged)) else None
+        resolved = False
+        for e in flagged:
+            try:
+                if not host_fallback:
+                    raise np.linalg.LinAlgError(f"mds_dlqr_omega_solve_gain: env {e} ended with status {self.care_status[e]}")
+                K[e] = self._are_gain(th[e, :m * D, :].T, th[e, m * D:, :].T, force_diagonal)
+                status[e] = resolved = True
+            except (np.linalg.LinAlgError, ValueError):
+                if E == 1:
+                    raise
+                K[e] = Kprev[e] if Kprev is not None else 0.0
+        self.are_status = status
+        self.K = self._one(K)
+        if resolved:                                                # the device already holds every other env's gain
+            self.upload_gain(K)
 
     def upload_gain(self, K):
         """K [4D,9D] (every env) or [E,4D,9D] -> the device (mds_set_dlqr_omega_gain)."""

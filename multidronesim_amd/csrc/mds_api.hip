@@ -21,6 +21,7 @@
 #include "mds_cbf_kernels.hip"      // (part 2 only: it defines a non-template kernel)
 #include "mds_fedce_kernels.hip"    // FedCE identification and the dLQR kernels (part 2 only)
 #include "mds_fedce_omega_kernels.hip"   // the same on the 9-state thrust / body-rate model (part 2 only)
+#include "mds_care_kernels.hip"     // the Riccati solver of both models' dLQR gains (part 2 only)
 #else
 #include "mds_cbf.hpp"
 #endif
@@ -173,6 +174,10 @@ struct mds_handle {
   double* fo_W = nullptr;         // [n][13][13]
   double* fo_theta = nullptr;     // [n][13][9]
   void* dlqr_omega_K = nullptr;   // T [E][4][9 D][D] (dlqr_kidx_m<9>)
+  // the device Riccati solver (mds_dlqr_solve_gain / mds_dlqr_omega_solve_gain), slot 0: 12-state, 1: 9-state
+  double* care_tab[2] = {nullptr, nullptr};      // R^-1 [D][16] | Q of every single [M, M] | Q of every pair [2M, 2M]
+  std::vector<double> care_tab_host[2];          // what care_tab holds: a call with the same Q and R uploads nothing
+  double* care_K64[2] = {nullptr, nullptr};      // [E, 4D, MD] float64 staging when the caller passes no K_dev
   bool track_rpm = false;        // last_rpm planes maintained by every step kernel (DYN_DRAG, order-3 CBF, or cfg.track_last_rpm)
   bool rpm_stale = false;        // a step ran without tracking since the last reset
 };
@@ -537,6 +542,10 @@ int mds_destroy(mds_handle* h) {
   if (h->fo_W) (void)hipFree(h->fo_W);
   if (h->fo_theta) (void)hipFree(h->fo_theta);
   if (h->dlqr_omega_K) (void)hipFree(h->dlqr_omega_K);
+  for (int k = 0; k < 2; ++k) {
+    if (h->care_tab[k]) (void)hipFree(h->care_tab[k]);
+    if (h->care_K64[k]) (void)hipFree(h->care_K64[k]);
+  }
   if (h->split_st) (void)hipStreamDestroy(h->split_st);
   for (int k = 0; k < 2; ++k)
     if (h->split_ev[k]) (void)hipEventDestroy(h->split_ev[k]);
@@ -2591,6 +2600,139 @@ int mds_rollout_dlqr_omega_fused(mds_handle* h, double t0, int n_steps, void* ob
   });
   MDS_HIP(hipGetLastError());
   return MDS_OK;
+}
+// ------------------------------------------------------------------------------------------------------------------------------
+// The dLQR gains on the device (mds_care_kernels.hip): one Riccati problem per (env, connected component of Q's block graph)
+// ------------------------------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+template <int M>
+static int care_solve_gain(mds_handle* h, const char* who, const double* Q, const double* R, int max_iter, double* K_dev, int32_t* status_dev,
+                           int32_t* iters_dev, void* stream) {
+  constexpr int slot = M == 12 ? 0 : 1;
+  char msg[256];
+  auto bad = [&](int code, const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(code, msg);
+  };
+  if (!h || !Q || !R || !status_dev) return bad(MDS_EINVAL, "null argument");
+  MDS_DEV(h);
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  const double* theta = M == 12 ? h->fedce_theta : h->fo_theta;
+  if (!theta) return bad(MDS_ESTATE, M == 12 ? "call mds_fedce_init first" : "call mds_fedce_omega_init first");
+  if (!aligned16(K_dev) || !aligned16(status_dev) || !aligned16(iters_dev)) return bad(MDS_EALIGN, "K_dev / status_dev / iters_dev");
+  if (max_iter <= 0) max_iter = kCareMaxIter;
+  const int E = h->cfg.num_envs, D = h->cfg.num_drones, nq = M * D, nr = 4 * D;
+  // R: block diagonal in 4 x 4 blocks, every block inverted on the host with the solver's own Gauss-Jordan routine
+  std::vector<double> tab((size_t)D * 16);
+  for (int i = 0; i < nr; ++i)
+    for (int j = 0; j < nr; ++j)
+      if (i / 4 != j / 4 && R[(size_t)i * nr + j] != 0.0) return bad(MDS_EUNSUPPORTED, "R is not block diagonal in 4 x 4 blocks per drone");
+  for (int d = 0; d < D; ++d) {
+    double a[4 * 9], mcol[4], lad;
+    int piv[4];
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) a[i * 9 + j] = R[(size_t)(4 * d + i) * nr + 4 * d + j];
+    if (!care_gj_inverse<9>(CareSerial{}, a, 4, mcol, piv, &lad)) return bad(MDS_EINVAL, "a 4 x 4 block of R is singular");
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) tab[(size_t)d * 16 + i * 4 + j] = a[i * 9 + j];
+  }
+  // Q: symmetric; the connected components of its M x M block graph are the problems
+  double qmax = 0.0;
+  for (size_t k = 0; k < (size_t)nq * nq; ++k) qmax = fmax(qmax, fabs(Q[k]));
+  for (int i = 0; i < nq; ++i)
+    for (int j = 0; j < i; ++j)
+      if (!(fabs(Q[(size_t)i * nq + j] - Q[(size_t)j * nq + i]) <= 1e-12 * qmax)) return bad(MDS_EINVAL, "Q is not symmetric");
+  int comp[kFedceMaxD];
+  for (int d = 0; d < D; ++d) comp[d] = d;
+  for (int a = 0; a < D; ++a)
+    for (int b = 0; b < a; ++b) {
+      bool linked = false;
+      for (int i = 0; i < M && !linked; ++i)
+        for (int j = 0; j < M && !linked; ++j) linked = Q[(size_t)(M * a + i) * nq + M * b + j] != 0.0;
+      if (linked && comp[a] != comp[b]) {
+        const int from = comp[a], to = comp[b];
+        for (int d = 0; d < D; ++d)
+          if (comp[d] == from) comp[d] = to;
+      }
+    }
+  CareGroups singles = {}, pairs = {};
+  for (int c = 0; c < D; ++c) {
+    int members[kFedceMaxD], cnt = 0;
+    for (int d = 0; d < D; ++d)
+      if (comp[d] == c) members[cnt++] = d;
+    if (cnt > 2 || (cnt == 2 && M != 12)) {
+      int at = snprintf(msg, sizeof(msg), "%s: Q couples drones", who);
+      for (int k = 0; k < cnt && at < (int)sizeof(msg) - 8; ++k) at += snprintf(msg + at, sizeof(msg) - at, " %d", members[k]);
+      snprintf(msg + at, sizeof(msg) - at, M == 12 ? ": components of more than two drones are not built" : ": coupled drones are not built for the 9-state model");
+      return fail(MDS_EUNSUPPORTED, msg);
+    }
+    if (cnt == 1) singles.drone[singles.count++][0] = members[0];
+    if (cnt == 2) {
+      pairs.drone[pairs.count][0] = members[0];
+      pairs.drone[pairs.count++][1] = members[1];
+    }
+  }
+  const size_t q1 = (size_t)D * 16, q2 = q1 + (size_t)singles.count * M * M;
+  tab.resize(q2 + (size_t)pairs.count * 4 * M * M);
+  for (int g = 0; g < singles.count; ++g)
+    for (int i = 0; i < M; ++i)
+      for (int j = 0; j < M; ++j) tab[q1 + ((size_t)g * M + i) * M + j] = Q[(size_t)(M * singles.drone[g][0] + i) * nq + M * singles.drone[g][0] + j];
+  for (int g = 0; g < pairs.count; ++g)
+    for (int i = 0; i < 2 * M; ++i)
+      for (int j = 0; j < 2 * M; ++j)
+        tab[q2 + ((size_t)g * 2 * M + i) * 2 * M + j] = Q[(size_t)(M * pairs.drone[g][i / M] + i % M) * nq + M * pairs.drone[g][j / M] + j % M];
+  // device side: the table (uploaded only when Q or R changed: a call with the same ones only enqueues), the staging K, the gain buffer
+  if (!h->care_tab[slot]) MDS_HIP(hipMalloc(&h->care_tab[slot], ((size_t)D * 16 + (size_t)D * M * M * 2) * sizeof(double)));    // the largest a table gets
+  if (h->care_tab_host[slot] != tab) {
+    MDS_HIP(hipDeviceSynchronize());
+    MDS_HIP(hipMemcpy(h->care_tab[slot], tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->care_tab_host[slot] = tab;
+  }
+  const size_t per = (size_t)nr * nq, total = per * E;
+  if (!K_dev) {
+    if (!h->care_K64[slot]) MDS_HIP(hipMalloc(&h->care_K64[slot], total * sizeof(double)));
+    K_dev = h->care_K64[slot];
+  }
+  void** gain = M == 12 ? &h->dlqr_K : &h->dlqr_omega_K;
+  const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  if (!*gain) {                                  // no gain yet: an env that fails keeps zeros
+    MDS_HIP(hipMalloc(gain, total * es));
+    MDS_HIP(hipMemsetAsync(*gain, 0, total * es, st));
+  }
+  MDS_HIP(hipMemsetAsync(K_dev, 0, total * sizeof(double), st));
+  MDS_HIP(hipMemsetAsync(status_dev, 0, (size_t)E * sizeof(int32_t), st));
+  if (iters_dev) MDS_HIP(hipMemsetAsync(iters_dev, 0, (size_t)E * sizeof(int32_t), st));
+  const double* Rinv_tab = h->care_tab[slot];
+  if (singles.count) {
+    constexpr int W = 2 * M, WAVES = CareShape<W>::WAVES;
+    const long np = (long)E * singles.count;
+    k_care_solve<W><<<dim3((unsigned)((np + WAVES - 1) / WAVES)), 64 * WAVES, 0, st>>>(E, D, singles, theta, Rinv_tab, Rinv_tab + q1, max_iter, K_dev,
+                                                                                        status_dev, iters_dev);
+  }
+  if constexpr (M == 12) {
+    if (pairs.count) {
+      const long np = (long)E * pairs.count;
+      k_care_solve<48><<<dim3((unsigned)np), 64, 0, st>>>(E, D, pairs, theta, Rinv_tab, Rinv_tab + q2, max_iter, K_dev, status_dev, iters_dev);
+    }
+  }
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (h->cfg.dtype == MDS_F64) k_care_commit<double, M><<<grid, 256, 0, st>>>(E, D, K_dev, status_dev, (double*)*gain);
+  else k_care_commit<float, M><<<grid, 256, 0, st>>>(E, D, K_dev, status_dev, (float*)*gain);
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+
+extern "C" {
+int mds_dlqr_solve_gain(mds_handle* h, const double* Q_host, const double* R_host, int max_iter, double* K_dev, int32_t* status_dev,
+                        int32_t* iters_dev, void* stream) {
+  return care_solve_gain<12>(h, "mds_dlqr_solve_gain", Q_host, R_host, max_iter, K_dev, status_dev, iters_dev, stream);
+}
+
+int mds_dlqr_omega_solve_gain(mds_handle* h, const double* Q_host, const double* R_host, int max_iter, double* K_dev, int32_t* status_dev,
+                              int32_t* iters_dev, void* stream) {
+  return care_solve_gain<kOmegaM>(h, "mds_dlqr_omega_solve_gain", Q_host, R_host, max_iter, K_dev, status_dev, iters_dev, stream);
 }
 #endif  // MDS_PART & 2
 

@@ -169,10 +169,11 @@ class GeometricEnv:
 
     # ------------------------------------------------------------------ FedCE (:113-325)
     def fedCE(self, num_iter=15, record_results=False, noise=None, generator=None, do_lemniscate=False, log_observations=False,
-              log_iterations=False):
+              log_iterations=False, riccati="host"):
         """-> (K, theta) of the last iteration, as the reference.  ``noise``: per iteration (u_warm [25,(E,)D,4] or None,
         u_explore [Texp,(E,)D,4]) raw draws instead of sigma1 / sigma_explore.  ``log_iterations`` keeps theta and K of every
-        iteration in fedce_thetas / fedce_Ks.  Closes the env like the reference (:151)."""
+        iteration in fedce_thetas / fedce_Ks.  ``riccati``: "host" (scipy, one env after the other) or "device" (every env at once),
+        passed to compute_controller(solver=...).  Closes the env like the reference (:151)."""
         from ..control import DecentralizedLQR
         env, D = self.env, self.args.num_drones
         dLQR = DecentralizedLQR(env, self.linear_models)
@@ -183,7 +184,8 @@ class GeometricEnv:
         self.fedce_thetas, self.fedce_Ks = [], []
         for n in range(num_iter):
             steps = self.fedCE_iteration(env, dLQR, START, steps, n, do_warmup=(n == 0), random_warmup=True, do_lemniscate=do_lemniscate,
-                                         noise=None if noise is None else noise[n], generator=generator, log_observations=log_observations)
+                                         noise=None if noise is None else noise[n], generator=generator, log_observations=log_observations,
+                                         riccati=riccati)
             if log_iterations:
                 self.fedce_thetas.append(dLQR.theta)
                 self.fedce_Ks.append(np.copy(dLQR.K))
@@ -218,7 +220,7 @@ class GeometricEnv:
         return dLQR.K, theta
 
     def fedCE_iteration(self, env, dLQR, START, steps, n, k=2, do_warmup=True, random_warmup=True, do_lemniscate=False, do_print=False,
-                        noise=None, generator=None, log_observations=False):
+                        noise=None, generator=None, log_observations=False, riccati="host"):
         """One FedCE iteration (:154-325): [25-step random warm-up], compute_controller, 4n CE steps, min(2n, 40) exploration steps,
         each phase one launch.  The reference's loop-variable quirk is kept: its `if i != 0` tests the wind loop's D - 1, so every
         step updates when D >= 2 and none when D == 1."""
@@ -245,7 +247,7 @@ class GeometricEnv:
                 logs.append(log)
             steps += Tw
         last_desired = np.zeros((D, 12))
-        dLQR.compute_controller()
+        dLQR.compute_controller(solver=riccati)
         if Tce:
             if do_lemniscate:
                 traj = Lemniscate(center=np.array([0, 0, .5]), omega=1, yaw_rate=.1)

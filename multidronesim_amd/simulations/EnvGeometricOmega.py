@@ -81,11 +81,13 @@ class GeometricEnv(_cbf.GeometricEnv):
         env.close()
 
     # ------------------------------------------------------------------ FedCE (:109-263)
-    def fedCE(self, num_iter=15, noise=None, generator=None, log_observations=False, log_iterations=False, log_updates=False, verbose=False):
+    def fedCE(self, num_iter=15, noise=None, generator=None, log_observations=False, log_iterations=False, log_updates=False, verbose=False,
+              riccati="host"):
         """-> (K, theta) of the last iteration, as the reference (:109-125).  ``noise``: per iteration (u_warm [25,(E,)D,4] or None,
         u_explore [Texp,(E,)D,4]) raw draws instead of sigma1 / sigma_explore.  ``log_iterations`` keeps theta, P and K of every
         iteration in fedce_thetas / fedce_Ps / fedce_Ks; ``log_observations`` every observation in fedce_observations; ``log_updates``
-        every drone's theta after every theta_update2 in fedce_theta_updates ([D,13,9] each, or [E,D,13,9])."""
+        every drone's theta after every theta_update2 in fedce_theta_updates ([D,13,9] each, or [E,D,13,9]).  ``riccati``: "host" (scipy,
+        one env after the other) or "device" (every env at once), passed to compute_controller(solver=...)."""
         from ..control import DecentralizedLQROmega
         env, args = self.env, self.args
         steps = 0
@@ -95,7 +97,7 @@ class GeometricEnv(_cbf.GeometricEnv):
         for n in range(num_iter):
             steps = self.fedCE_iteration(env, dLQR, START, steps, n, do_warmup=(n == 0), random_warmup=True,
                                          noise=None if noise is None else noise[n], generator=generator, log_observations=log_observations,
-                                         log_updates=log_updates)
+                                         log_updates=log_updates, riccati=riccati)
             if log_iterations:
                 self.fedce_thetas.append(dLQR.theta)
                 self.fedce_Ps.append(dLQR.P)
@@ -113,7 +115,7 @@ class GeometricEnv(_cbf.GeometricEnv):
         return dLQR.K, theta
 
     def fedCE_iteration(self, env, dLQR, START, steps, n, k=2, do_warmup=True, random_warmup=True, do_lemniscate=False, do_print=False,
-                        noise=None, generator=None, log_observations=False, log_updates=False):
+                        noise=None, generator=None, log_observations=False, log_updates=False, riccati="host"):
         """One FedCE iteration (:127-263): the zero-action step, [25-step random warm-up], compute_controller, Tce = n k^3 CE steps
         towards the targets, Texp = n k exploration steps around last_desired; each phase one launch, theta_update2 on every step of
         a phase but its first (`if i != 0`)."""
@@ -136,7 +138,7 @@ class GeometricEnv(_cbf.GeometricEnv):
                 logs.append(log)
             steps += Tw
         last_desired = np.zeros((D, 9))
-        dLQR.compute_controller()
+        dLQR.compute_controller(solver=riccati)
         if Tce:
             if do_lemniscate:
                 env.set_trajectories([Lemniscate(center=np.array([0, 0, .5]), omega=1, yaw_rate=.1)] * D)
