@@ -191,23 +191,74 @@ template <bool KEEP> __device__ __forceinline__ void store_chunk(v4u_t v, v4u_t*
 // KEEP: default-policy stores instead of non-temporal ones -- for a destination that is REWRITTEN every control step
 // (the whole-rollout kernels with obs_every_step: the same [n, 20] array, 42 MB at config 3's size): the lines stay in the L2 / Infinity
 // Cache between the steps of a launch instead of going out to HBM each time (measured, C3, 2000 steps: 10.5 -> 8.6 us per control step).
-// FRESH (the whole-rollout kernels, which call this once per step of a loop they never leave): the lane's LDS and global offsets and the
-// bound masks are formed from the thread index here, at every call, instead of being hoisted out of the step loop and held across it
-// (64-bit per-lane addresses and five masks per expansion); the wave's span is addressed as a scalar base + a 32-bit lane offset.
+// FRESH (the whole-rollout kernels, which call this once per step of a loop they never leave): the bound masks and the addresses are
+// formed here, at every call, instead of being hoisted out of the step loop and held across it (64-bit per-lane addresses and five
+// masks per expansion); the wave's span is addressed as a scalar base + a 32-bit lane offset.
+//
+// ObsRowOffs: what the addressing needs of the thread index -- two per-lane byte offsets into the workgroup's staging block (the lane's
+// row, the lane's first 16-byte chunk) and two wave-uniform values.  A wave's slice of the block and its span of the rows are the same
+// bytes in the same order, so the chunk offset serves the LDS read and, against a scalar base, the global store.  A FRESH caller that
+// forms them once before its loop (`pre`) pays two VGPRs for them and no integer VALU per step.
+struct ObsRowOffs {
+  unsigned lds_w, lds_r;       // per lane: wave_lds + lane * row bytes, wave_lds + lane * 16
+  int wave_lds, wave_base;     // wave-uniform: byte offset of the wave's slice, first drone of the wave
+};
+template <typename S, bool UNIFORM> __device__ __forceinline__ ObsRowOffs obs_row_offs(int i, unsigned tid) {
+  constexpr int kRowBytes = kObsDim * (int)sizeof(S);
+  const unsigned lane = tid & (unsigned)(kWave - 1);
+  ObsRowOffs r;
+  // the wave index on the scalar side: no vector multiply.  For every caller, the per-step and CBF kernels included: all launch 1-D
+  // workgroups of whole waves and call this converged, so tid >> 6 is wave-uniform
+  r.wave_lds = uniform_i32((int)(tid >> 6)) * (kWave * kRowBytes);
+  r.lds_w = (unsigned)r.wave_lds + lane * (unsigned)kRowBytes;
+  r.lds_r = (unsigned)r.wave_lds + lane * 16u;
+  r.wave_base = UNIFORM ? uniform_i32(i - (int)lane) : i - (int)lane;
+  return r;
+}
+// the scalar base of a lane's chunk `it`: the store's offset field reaches 4 KiB, so every fourth chunk starts a base of its own (formed
+// on the scalar side; OPAQUE keeps the optimiser from folding it back into the lane offset as a vector add)
+template <bool OPAQUE> __device__ __forceinline__ unsigned char* span_base(unsigned char* gdst, int it) {
+  unsigned skip = (unsigned)(it / 4) * (4 * kWave * 16);
+  if (OPAQUE && it >= 4) MDS_KEEP_S(skip);
+  return gdst + skip;
+}
 template <typename S, typename T, bool KEEP = false, bool FRESH = false>
 __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_block, S* __restrict__ obs, int n, int i,
-                                               bool valid, const T o[kObsDim]) {
+                                               bool valid, const T o[kObsDim], ObsRowOffs* pre = nullptr) {
   constexpr int kRowBytes = kObsDim * (int)sizeof(S);           // 80 / 160 / 40
   constexpr int kUnit = (kRowBytes % 16 == 0) ? 16 : 8;          // widest aligned LDS store per row
-  int tid = (int)threadIdx.x;
-  if (FRESH) MDS_KEEP_V(tid);
-  const int lane = tid & (kWave - 1);
-  const int wave = tid / kWave;
-  unsigned char* lds_wave = lds_block + wave * (kWave * kRowBytes);
+  // Which copy of the offsets is which: `*pre` is the authoritative one -- the caller's loop-carried struct, or `formed` when the caller
+  // passed none.  The two per-lane offsets are read THROUGH `pre`, and a FRESH caller's are made opaque in place (MDS_KEEP_V on the
+  // caller's own variable: the value passes through the same register; on a copy it would cost a v_mov and a second register per step).
+  // `ro` is a by-value copy used for lds_w and the two scalars only; the scalars are made opaque on the copy, because an asm output that
+  // feeds the loop-carried value back is treated as divergent, and a scalar copy costs no vector instruction.
+  ObsRowOffs formed;
+  if (pre == nullptr) {
+    unsigned tid = threadIdx.x;
+    if (FRESH) MDS_KEEP_V(tid);
+    formed = obs_row_offs<S, FRESH>(i, tid);
+    pre = &formed;
+  } else if (FRESH) {                                            // (what is derived from the offsets is formed here, not held across the loop;
+    MDS_KEEP_V(pre->lds_w);                                      //  the caller's own copies pass through: no second register for them)
+  }
+  ObsRowOffs ro = *pre;
+  if (FRESH && pre != &formed) {                                 // (scalar copies cost no vector instruction)
+    MDS_KEEP_S(ro.wave_lds);
+    MDS_KEEP_S(ro.wave_base);
+  }
+  // the lane's chunk offset, fresh in the block that uses it: the 32-bit offset is extended next to the stores, which then take the scalar
+  // base + lane offset form, and + it * 1024 folds into the instructions' offset fields
+  auto chunk_offs = [&](bool full) {
+    if (FRESH && pre != &formed && full) MDS_KEEP_V(pre->lds_r);       // (the full-wave arm: the one every wave but the shard's last takes)
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_assume(pre->lds_r < (unsigned)(kBlock * kRowBytes));
+#endif
+    return pre->lds_r;
+  };
   if (valid) {
     alignas(16) S row[kObsDim];
     for (int k = 0; k < kObsDim; ++k) row[k] = (S)o[k];
-    unsigned char* dst = lds_wave + lane * kRowBytes;
+    unsigned char* dst = lds_block + ro.lds_w;
     if (kUnit == 16) {
       for (int k = 0; k < kRowBytes / 16; ++k) reinterpret_cast<uint4*>(dst)[k] = reinterpret_cast<const uint4*>(row)[k];
     } else {
@@ -219,37 +270,44 @@ __device__ __forceinline__ void write_obs_rows(unsigned char* __restrict__ lds_b
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int wave_base = FRESH ? uniform_i32(i - lane) : i - lane;   // first drone of this wave
+  const int wave_base = ro.wave_base;                            // first drone of this wave
   const int rows = min(kWave, n - wave_base);                    // <= 0 for fully invalid waves
   typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   constexpr int kIters = (kWave * kRowBytes + kWave * 16 - 1) / (kWave * 16);
   constexpr int kFull = (kWave * kRowBytes) / (kWave * 16);       // iterations in which all 64 lanes have a chunk of a full wave's rows
   if (rows >= kWave) {
+    const unsigned lds_r = chunk_offs(true);
+    const int lane16 = (int)(lds_r - (unsigned)ro.wave_lds);     // byte offset of the lane's first chunk in the wave's slice
+    const unsigned char* lds_chunk = lds_block + lds_r;          // the lane's chunk `it` is at + it * kWave * 16, in LDS and in the span
     // a full wave (every wave but the shard's last): all LDS reads in flight at once, then the stores -- no per-chunk bounds test, one
     // LDS round trip instead of kIters serial ones
-    unsigned char* gdst = reinterpret_cast<unsigned char*>(obs) + (size_t)wave_base * kRowBytes;
+    unsigned char* gdst = reinterpret_cast<unsigned char*>(obs) + ((size_t)wave_base * kRowBytes - (size_t)ro.wave_lds);
     constexpr int kGroup = 5;                                    // chunks in flight per lane (20 VGPRs)
 #pragma unroll
     for (int g = 0; g < kIters; g += kGroup) {
       v4u tmp[kGroup];
 #pragma unroll
       for (int it = g; it < kIters && it < g + kGroup; ++it)
-        if (it < kFull || lane * 16 + 16 <= kWave * kRowBytes - it * kWave * 16) tmp[it - g] = *reinterpret_cast<const v4u*>(lds_wave + (it * kWave + lane) * 16);
+        if (it < kFull || lane16 + 16 <= kWave * kRowBytes - it * kWave * 16) tmp[it - g] = *reinterpret_cast<const v4u*>(lds_chunk + it * kWave * 16);
 #pragma unroll
       for (int it = g; it < kIters && it < g + kGroup; ++it)
-        if (it < kFull || lane * 16 + 16 <= kWave * kRowBytes - it * kWave * 16)
-            store_chunk<KEEP>(tmp[it - g], reinterpret_cast<v4u*>(gdst + (unsigned)((it * kWave + lane) * 16)));
+        if (it < kFull || lane16 + 16 <= kWave * kRowBytes - it * kWave * 16)
+            store_chunk<KEEP>(tmp[it - g], reinterpret_cast<v4u*>(span_base<FRESH>(gdst, it) + (lds_r + (unsigned)((it % 4) * kWave * 16))));
     }
   } else if (rows > 0) {
     const int bytes = rows * kRowBytes;                          // multiple of 8; of 16 unless half with odd rows
-    unsigned char* gdst = reinterpret_cast<unsigned char*>(obs) + (size_t)wave_base * kRowBytes;
+    const unsigned lds_r = chunk_offs(false);
+    const int lane16 = (int)(lds_r - (unsigned)ro.wave_lds);
+    const unsigned char* lds_chunk = lds_block + lds_r;
+    unsigned char* gdst = reinterpret_cast<unsigned char*>(obs) + ((size_t)wave_base * kRowBytes - (size_t)ro.wave_lds) + lds_r;
+#pragma unroll
     for (int it = 0; it < kIters; ++it) {
-      const int off = (it * kWave + lane) * 16;
+      const int off = it * kWave * 16 + lane16;                  // in the wave's slice
       if (off + 16 <= bytes) {
         // write-once stream: non-temporal (measured +3..6 % on MI355X vs default-policy stores)
-        __builtin_nontemporal_store(*reinterpret_cast<const v4u*>(lds_wave + off), reinterpret_cast<v4u*>(gdst + off));
-      } else if (off + 8 <= bytes) {                             // 8-byte tail (fp16 rows, odd row count)
-        *reinterpret_cast<uint2*>(gdst + off) = *reinterpret_cast<const uint2*>(lds_wave + off);
+        __builtin_nontemporal_store(*reinterpret_cast<const v4u*>(lds_chunk + it * kWave * 16), reinterpret_cast<v4u*>(gdst + it * kWave * 16));
+      } else if (kUnit == 8 && off + 8 <= bytes) {                             // 8-byte tail (fp16 rows, odd row count)
+        *reinterpret_cast<uint2*>(gdst + it * kWave * 16) = *reinterpret_cast<const uint2*>(lds_chunk + it * kWave * 16);
       }
     }
   }
@@ -692,9 +750,10 @@ __global__ void k_traj_eval(const int n, const double t, const SegTable segs, co
 // re-forms per step what costs a few instructions (products of the trajectory parameters and of the constants, the addresses),
 // reads the constants through the kernarg segment where they are used, and keeps the time in SGPRs.
 constexpr int kObsLast = 0, kObsInPlace = 1, kObsLog = 2;
-// waves per SIMD the register allocator is asked for: the fp32 Euler loops fit 6 (<= 80 VGPRs) without spilling; the others are left alone
+// waves per SIMD the register allocator is asked for: the fp32 Euler loops that write rows every step fit 6 (<= 80 VGPRs) without
+// spilling, the one that writes the last step's only (no frame carried, a step body of its own) 5 (<= 96); the others are left alone
 template <typename T, bool RK4, bool DRAG, int CTRL, int COMP, int OBS> constexpr int rollout_min_waves() {
-  return (sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0 && COMP == 0 && (OBS == kObsInPlace || OBS == kObsLog)) ? 6 : 1;
+  return !(sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0 && COMP == 0) ? 1 : (OBS == kObsInPlace || OBS == kObsLog) ? 6 : OBS == kObsLast ? 5 : 1;
 }
 template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0, int COMP = -1, int OBS = -1>
 __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP, OBS>())) void k_rollout_geometric(
@@ -709,29 +768,36 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
   constexpr bool kLean = !RK4 && COMP != 1;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   const bool valid = i < n;
+  if (n <= 0) return;          // (no drone to clamp to; the library launches no workgroup then)
+  // Whole-wave step body: the lanes past the last drone (the shard's last wave, and the empty waves of its workgroup) fly a copy of
+  // drone n - 1 -- every load at the clamped index, no store -- so the step loop runs without an exec-mask region around it and the
+  // rows need no copies at its join.  The wave-uniform short arms vote as the valid lanes do: the copy votes with its original.
+  const size_t il = (size_t)min(i, n - 1);
   GeoIn<T> in;
   resid_zero(in.r);            // compensated accumulation: all 13 residuals in registers (dead otherwise)
-  if (valid && comp) load_resid<S, T>(state_lo, ld, i, in.r);
+  if (comp) load_resid<S, T>(state_lo, ld, il, in.r);
   T prev[4] = {T(0), T(0), T(0), T(0)};        // DRAG: the previous step's clipped RPM, as the drag term reads it
   T thr[4] = {T(0), T(0), T(0), T(0)};         // CTRL 3: the same, as calc_z_thrust(obs) of the yank controller reads it
   LowLevelState<T> L;
   L.last_omega = L.integral = {T(0), T(0), T(0)};
-  if (valid) {
-    load_geo_in<T, S>(state, lem, ld, i, in);
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    if (CTRL >= 2) {
-      L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-      L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
-      if (CTRL == 3) load4<S, T>(obs_prev + (size_t)i * kObsDim + 16, thr);      // calc_z_thrust(obs) of the first step
-    }
+  load_geo_in<T, S>(state, lem, ld, il, in);
+  if (DRAG)
+    for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + il];
+  if (CTRL >= 2) {
+    L.last_omega = {ll[0 * ld + il], ll[1 * ld + il], ll[2 * ld + il]};
+    L.integral = {ll[3 * ld + il], ll[4 * ld + il], ll[5 * ld + il]};
+    if (CTRL == 3) load4<S, T>(obs_prev + il * kObsDim + 16, thr);      // calc_z_thrust(obs) of the first step
   }
   // CTRL 0: the frame of the state is carried across the step loop -- the one formed for step k's observation row (the state after
   // step k) is the one step k + 1's controller and rigid-body step read.  Where only the last step's rows leave (kObsLast) there is no
   // row to share it with: the frame is formed at the top of the step, as in k_step_geometric (the same values either way).
   constexpr bool kCarry = CTRL == 0 && OBS != kObsLast;
   Frame<T> F;
-  if (kCarry && valid) F = make_frame(in.s.q, in.s.w);
+  if (kCarry) F = make_frame(in.s.q, in.s.w);
+  // the row writer's offsets: formed once, two VGPRs held across the loop, the wave's first drone and slice wave-uniform (the lean loops
+  // re-form what derives from them per step; the others hoist what they like, from scalar bases now)
+  ObsRowOffs row_offs = obs_row_offs<S, true>(i, threadIdx.x);
+  ObsRowOffs* const ro = OBS != kObsLast ? &row_offs : nullptr;
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     const bool last = k == n_steps - 1;
@@ -744,61 +810,57 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
 #else
     const Consts<T>& c = c_arg;
 #endif
-    if (valid) {
-      T act[4], clipped[4];
-      {
-        // (per-lane parameters: what lemniscate_local derives from them is formed here every step, not held across the loop)
-        if (kLean) {
-          MDS_KEEP_V(in.P.a);
-          MDS_KEEP_V(in.P.omega);
-          MDS_KEEP_V(in.P.yaw_rate);
-          MDS_KEEP_V(in.P.phase_shift);
+    T act[4], clipped[4];
+    {
+      // (per-lane parameters: what lemniscate_local derives from them is formed here every step, not held across the loop)
+      if (kLean) {
+        MDS_KEEP_V(in.P.a);
+        MDS_KEEP_V(in.P.yaw_rate);
+      }
+      const Desired<T> des = lemniscate_local(in.P, t);
+      T u[4];
+      if (CTRL == 0) {
+        if (!kCarry) {
+          F = make_frame(in.s.q, in.s.w);
+        } else if (kLean) {    // R22 is not carried beside R22 - 1: 1 + (-a) is the 1 - a of make_frame to the bit
+          MDS_KEEP_V(F.r22m1);
+          F.R.m[8] = T(1) + F.r22m1;
         }
-        const Desired<T> des = lemniscate_local(in.P, t);
-        T u[4];
-        if (CTRL == 0) {
-          if (!kCarry) {
-            F = make_frame(in.s.q, in.s.w);
-          } else if (kLean) {    // R22 is not carried beside R22 - 1: 1 + (-a) is the 1 - a of make_frame to the bit
-            MDS_KEEP_V(F.r22m1);
-            F.R.m[8] = T(1) + F.r22m1;
-          }
-          geometric_control<T>(c, in.s.p - des.p, F.R, in.s.v, F.av, des, u, nullptr);
-        } else if (CTRL == 1) {
-          lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(in.s.q), quat_rotate(in.s.q, in.s.w), in.s.v, in.s.p - des.p,
-                           des.v, des.yaw, des.yaw_rate, u);
-        } else if (CTRL == 2) {
-          lqr_omega_control<T>(c, *static_cast<const LqrGain<T>*>(Kp), euler_from_quat(in.s.q), in.s.v, in.s.p, des.p, des.v, des.yaw, u);
-        } else {
-          lqr_yank_omega_control<T>(c, *static_cast<const LqrYoGain<T>*>(Kp), euler_from_quat(in.s.q), thr, in.s.v, in.s.p, des.p, des.v,
-                                    des.yaw, u);
-        }
-        if (CTRL <= 1) input_to_action(c, u, act);
-        else if (CTRL == 2) thrust_omega_control(c, (T)ctrl_dt, u, in.s.w, L, act);
-        else yank_omega_control(c, (T)ctrl_dt, u, thr, in.s.w, L, act);
+        geometric_control<T>(c, in.s.p - des.p, F.R, in.s.v, F.av, des, u, nullptr);
+      } else if (CTRL == 1) {
+        lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(in.s.q), quat_rotate(in.s.q, in.s.w), in.s.v, in.s.p - des.p,
+                         des.v, des.yaw, des.yaw_rate, u);
+      } else if (CTRL == 2) {
+        lqr_omega_control<T>(c, *static_cast<const LqrGain<T>*>(Kp), euler_from_quat(in.s.q), in.s.v, in.s.p, des.p, des.v, des.yaw, u);
+      } else {
+        lqr_yank_omega_control<T>(c, *static_cast<const LqrYoGain<T>*>(Kp), euler_from_quat(in.s.q), thr, in.s.v, in.s.p, des.p, des.v,
+                                  des.yaw, u);
       }
-      // (compensated storage and RK4 form their own thrust direction: there the frame serves the controller and the row only)
-      if (comp) aviary_step_comp<T, RK4, DRAG>(c, in.s, in.r, act, prev, clipped);
-      else if (CTRL == 0) aviary_step<T, RK4, DRAG>(c, in.s, F, act, prev, clipped);
-      else aviary_step<T, RK4, DRAG>(c, in.s, act, prev, clipped);
-      if (CTRL == 3)
-        for (int j = 0; j < 4; ++j) thr[j] = clipped[j];
-      if (kCarry) {
-        F = make_frame(in.s.q, in.s.w);
-        if (want) pack_obs(in.s, F, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
-      } else if (want) {
-        pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
-      }
-      // the clipped RPM leaves with the last step (not carried to the end of the loop)
-      if (last && (DRAG || last_rpm)) {
-        unsigned iu = (unsigned)i;
-        MDS_KEEP_V(iu);                              // (the planes' addresses are formed here, not held across the loop)
-        for (int j = 0; j < 4; ++j) *lane_ptr(last_rpm + j * ld, iu) = DRAG ? prev[j] : clipped[j];
-      }
+      if (CTRL <= 1) input_to_action(c, u, act);
+      else if (CTRL == 2) thrust_omega_control(c, (T)ctrl_dt, u, in.s.w, L, act);
+      else yank_omega_control(c, (T)ctrl_dt, u, thr, in.s.w, L, act);
     }
-    if (omode == kObsInPlace) write_obs_rows<S, T, true, kLean>(lds, obs_log, n, i, valid, o);       // the same rows rewritten every step: keep them cached
-    else if (omode == kObsLog) write_obs_rows<S, T, false, kLean>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o);
-    if (omode != kObsInPlace && obs_last != nullptr && last) write_obs_rows<S, T, false, kLean>(lds, obs_last, n, i, valid, o);
+    // (compensated storage and RK4 form their own thrust direction: there the frame serves the controller and the row only)
+    if (comp) aviary_step_comp<T, RK4, DRAG>(c, in.s, in.r, act, prev, clipped);
+    else if (CTRL == 0) aviary_step<T, RK4, DRAG>(c, in.s, F, act, prev, clipped);
+    else aviary_step<T, RK4, DRAG>(c, in.s, act, prev, clipped);
+    if (CTRL == 3)
+      for (int j = 0; j < 4; ++j) thr[j] = clipped[j];
+    if (kCarry) {
+      F = make_frame(in.s.q, in.s.w);
+      if (want) pack_obs(in.s, F, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
+    } else if (want) {
+      pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
+    }
+    // the clipped RPM leaves with the last step (not carried to the end of the loop)
+    if (valid && last && (DRAG || last_rpm)) {
+      unsigned iu = (unsigned)i;
+      MDS_KEEP_V(iu);                              // (the planes' addresses are formed here, not held across the loop)
+      for (int j = 0; j < 4; ++j) *lane_ptr(last_rpm + j * ld, iu) = DRAG ? prev[j] : clipped[j];
+    }
+    if (omode == kObsInPlace) write_obs_rows<S, T, true, kLean>(lds, obs_log, n, i, valid, o, ro);       // the same rows rewritten every step: keep them cached
+    else if (omode == kObsLog) write_obs_rows<S, T, false, kLean>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o, ro);
+    if (omode != kObsInPlace && obs_last != nullptr && last) write_obs_rows<S, T, false, kLean>(lds, obs_last, n, i, valid, o, ro);
     t = uniform_f64(t + ctrl_dt);
   }
   if (valid) {

@@ -1,7 +1,7 @@
 // VALU issue-rate microbenchmark for gfx950: cycles per wave64 instruction for scalar and packed fp32, dependent and independent chains,
 // and for the instruction classes the rollout step loop spends its slots on besides v_fma_f32 (compare-and-select pairs with their
-// hazard s_nop, v_med3_f32, v_max_f32 with an SGPR operand, v_mov_b32 from an SGPR, s_nop 1, v_rsq_f32, v_fma_f64), at 1..8 waves
-// per SIMD.  Build: hipcc --offload-arch=gfx950 -O3 -o valu_rate valu_rate.hip ; run: ./valu_rate
+// hazard s_nop, v_med3_f32, v_max_f32 with an SGPR operand, v_mov_b32 from an SGPR, s_nop 1, v_rsq_f32, v_fma_f64, and the bookkeeping
+// classes: v_mul_lo_u32, v_cvt_f64_f32, v_add_f64, v_readfirstlane_b32, v_lshl_add_u64), at 1..8 waves per SIMD.  Build: hipcc --offload-arch=gfx950 -O3 -o valu_rate valu_rate.hip ; run: ./valu_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -62,6 +62,26 @@ template <int MODE> __global__ void k(float* out, unsigned long long* cyc, int i
         d0 = fma(d0, dm, dc); d1 = fma(d1, dm, dc); d2 = fma(d2, dm, dc); d3 = fma(d3, dm, dc);
       } else if (MODE == 13) {  // the compare-and-select pair with two independent instructions between, as a scheduler would hide the hazard
         ASM8("v_cmp_lt_f32_e32 vcc, %1, %0\n\tv_max_f32_e32 %0, %0, %0\n\tv_max_f32_e32 %0, %0, %0\n\tv_cndmask_b32_e32 %0, %2, %0, vcc", "s"(slo), "v"(vlo) : "vcc");
+      } else if (MODE == 14) {  // v_mul_lo_u32 with an SGPR factor (the row writer's wave * 5120), 8 independent
+        ASM8("v_mul_lo_u32 %0, %0, %1", "s"(slo));
+      } else if (MODE == 15) {  // v_cvt_f64_f32 (the double copies of the trajectory parameters), 8 conversions into 4 register pairs
+        asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d0) : "v"(a0)); asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d1) : "v"(a1));
+        asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d2) : "v"(a2)); asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d3) : "v"(a3));
+        asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d0) : "v"(a4)); asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d1) : "v"(a5));
+        asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d2) : "v"(a6)); asm volatile("v_cvt_f64_f32_e32 %0, %1" : "=v"(d3) : "v"(a7));
+      } else if (MODE == 16) {  // v_add_f64 (the time's t + dt), 4 independent chains, two rounds
+        d0 = d0 + dc; d1 = d1 + dc; d2 = d2 + dc; d3 = d3 + dc; d0 = d0 + dc; d1 = d1 + dc; d2 = d2 + dc; d3 = d3 + dc;
+      } else if (MODE == 17) {  // v_readfirstlane_b32 into 8 SGPRs
+        int s0, s1, s2, s3, s4, s5, s6, s7;
+        asm volatile("v_readfirstlane_b32 %0, %8\n\tv_readfirstlane_b32 %1, %9\n\tv_readfirstlane_b32 %2, %10\n\tv_readfirstlane_b32 %3, %11\n\t"
+                     "v_readfirstlane_b32 %4, %12\n\tv_readfirstlane_b32 %5, %13\n\tv_readfirstlane_b32 %6, %14\n\tv_readfirstlane_b32 %7, %15"
+                     : "=s"(s0), "=s"(s1), "=s"(s2), "=s"(s3), "=s"(s4), "=s"(s5), "=s"(s6), "=s"(s7)
+                     : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(a6), "v"(a7));
+      } else if (MODE == 18) {  // v_lshl_add_u64 (a 64-bit per-lane address), 4 independent register pairs, two rounds
+        asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d0) : "v"(d1)); asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d1) : "v"(d2));
+        asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d2) : "v"(d3)); asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d3) : "v"(d0));
+        asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d0) : "v"(d1)); asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d1) : "v"(d2));
+        asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d2) : "v"(d3)); asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(d3) : "v"(d0));
       }
     }
   }
@@ -105,6 +125,11 @@ int main() {
     run<10>("s_nop 1", w);
     run<11>("v_rsq_f32, 8 independent", w);
     run<12>("v_fma_f64, 4 independent", w);
+    run<14>("v_mul_lo_u32, SGPR factor", w);
+    run<15>("v_cvt_f64_f32", w);
+    run<16>("v_add_f64, 4 independent", w);
+    run<17>("v_readfirstlane_b32", w);
+    run<18>("v_lshl_add_u64", w);
   }
   return 0;
 }
