@@ -267,7 +267,9 @@ int mds_get_last_rollout_form(const mds_handle* h);
  * registers between steps; every step's observation is streamed to obs_log_dev [n_steps, n, 20]
  * (the reference's `observations.append(obs)` -> np.save, EnvGeometric.py:471,553) when it is not
  * NULL; obs_last_dev [n,20] (or NULL) receives the final observation.  Lemniscate planes or segment tables.  Same arithmetic as n_steps
- * calls of mds_step_geometric (results agree to rounding: the two kernels may contract FMAs differently). */
+ * calls of mds_step_geometric (results agree to rounding: the two kernels may contract FMAs differently).
+ * Every slot of the log must start 16-byte aligned: with obs_log_dev, n_steps > 1 and n * 20 * element size not a multiple of 16 --
+ * only fp16 storage with an odd n -- the call is refused with MDS_EALIGN, as mds_rollout_step refuses such a ring. */
 int mds_rollout_geometric_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_last_dev, void* stream);
 
 /* ---- stand-alone per-drone operators (same arithmetic as the fused path) ---------------- */
@@ -421,7 +423,8 @@ int mds_lqr_compute(mds_handle* h, const void* obs_dev, const void* des_dev, voi
 /* The do_control step of simulations/EnvGeometric.py:434-469 with that controller for every drone: trajectory sample ->
  * LQRController.compute -> env.step.  Trajectories as for mds_step_geometric (Lemniscate planes or segment tables). */
 int mds_step_lqr(mds_handle* h, double t, void* obs_dev, void* action_dev, void* stream);
-/* n_steps of that loop in ONE launch (Lemniscate trajectories), as mds_rollout_geometric_fused does for the geometric controller */
+/* n_steps of that loop in ONE launch (Lemniscate trajectories), as mds_rollout_geometric_fused does for the geometric controller
+ * (and with its refusal: a log of more than one step on fp16 storage with an odd n is MDS_EALIGN) */
 int mds_rollout_lqr_fused(mds_handle* h, double t0, int n_steps, void* obs_log_dev, void* obs_last_dev, void* stream);
 
 /* LQRYankOmegaController (control/lqr/lqr_YO_controller.py): K [4,10] row-major from its

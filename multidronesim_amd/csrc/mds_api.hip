@@ -1263,6 +1263,10 @@ int rollout_fused(mds_handle* h, double t0, int n_steps, void* obs_log, void* ob
     if (!obs_last) return fail(MDS_EINVAL, "mds_rollout_nominal_fused: obs_dev is required (in: current observation, out: last one)");
   }
   if (!aligned16(obs_log) || !aligned16(obs_last)) return fail(MDS_EALIGN, "mds_rollout_*_fused: obs buffers");
+  // step k's rows start n * 20 elements behind step k - 1's and go out in 16-byte chunks: fp16 storage with an odd n is the one case
+  // in which a slot of the log can start off a 16-byte boundary
+  if (obs_log && n_steps > 1 && ((size_t)h->n * kObsDim * elem_size(h->cfg.dtype)) % 16)
+    return fail(MDS_EALIGN, "mds_rollout_*_fused: obs_log_dev (every action set and log slot must start 16-byte aligned)");
   if (n_steps == 0) return MDS_OK;
   launch_rollout_kernel(h, ctrl, t0, n_steps, obs_log, (size_t)h->n * kObsDim, obs_last, (hipStream_t)stream);
   MDS_HIP(hipGetLastError());

@@ -415,7 +415,8 @@ class BaseAviary:
         """``n_steps`` fused control steps in ONE kernel launch (state stays in registers).  With
         ``log`` every step's observation goes to a [T,E,D,20] tensor (the reference's
         ``observations.append(obs)``, EnvGeometric.py:471); returns (last obs, log or None).  ``controller="lqr"`` runs the
-        12-state LQRController (constructed on this env) instead of GeometricControl."""
+        12-state LQRController (constructed on this env) instead of GeometricControl.  Every step's slot of the log must start
+        16-byte aligned: a log of more than one step on a ``float16`` env with an odd number of drones is refused (MDS_EALIGN)."""
         self._require_open()
         if log and log_out is None:
             log_out = torch.empty((n_steps, self.NUM_ENVS, self.NUM_DRONES, capi.OBS_DIM), dtype=self.dtype, device=self.device)
