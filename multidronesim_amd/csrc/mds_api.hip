@@ -14,6 +14,7 @@
 #include "../../include/mds.h"
 #include "mds_consts.hpp"
 #include "mds_kernels.hip"
+#include "mds_traj_image.hpp"
 #ifndef MDS_PART
 #define MDS_PART 3
 #endif
@@ -808,98 +809,13 @@ int mds_set_trajectory_segments(mds_handle* h, const double* segs, const int32_t
   MDS_DEV(h);
   if (!h || !segs || !offsets || !compound || !anchor) return fail(MDS_EINVAL, "mds_set_trajectory_segments: null argument");
   const int n = h->n;
-  if (total <= 0 || offsets[0] != 0 || offsets[n] != total) return fail(MDS_EINVAL, "mds_set_trajectory_segments: offsets");
-  for (int i = 0; i < n; ++i) {
-    const int ns = offsets[i + 1] - offsets[i];
-    if (ns < 1 || ns > 65535) return fail(MDS_EINVAL, "mds_set_trajectory_segments: every drone needs 1..65535 segments");
-  }
-  for (int k = 0; k < total; ++k) {
-    const int kind = (int)segs[(size_t)k * MDS_SEG_DIM];
-    if (kind < 0 || kind > 3) return fail(MDS_EINVAL, "mds_set_trajectory_segments: segment kind");
-  }
-  // Drones that follow identical tables (the same trajectory objects broadcast over every env) share one device copy:
-  // the table then stays in L2 instead of costing up to 300 B of HBM reads per drone-step.  Unique tables with the same
-  // number of pieces form a block stored piece-major (TrajInfo), and the image is field-major (SegTable).
-  std::vector<int> ti((size_t)3 * n), uniq_of((size_t)n), usrc, uns;     // usrc/uns: first source row / piece count of a unique table
+  // validation, de-duplication and the field-major / piece-major image: host code of its own (csrc/mds_traj_image.hpp)
+  std::vector<int> ti;
   std::vector<double> fm;
   int nu = 0;
-  try {
-    std::unordered_multimap<uint64_t, int> seen;        // hash of a drone's rows -> unique table
-    for (int i = 0; i < n; ++i) {
-      const int ns = offsets[i + 1] - offsets[i];
-      const unsigned char* bytes = reinterpret_cast<const unsigned char*>(segs + (size_t)offsets[i] * MDS_SEG_DIM);
-      const size_t nbytes = sizeof(double) * MDS_SEG_DIM * (size_t)ns;
-      uint64_t hsh = 1469598103934665603ull ^ (uint64_t)ns;
-      for (size_t w = 0; w < nbytes; w += 8) {
-        uint64_t word;
-        memcpy(&word, bytes + w, 8);
-        hsh = (hsh ^ word) * 1099511628211ull;
-        hsh ^= hsh >> 29;
-      }
-      int u = -1;
-      auto range = seen.equal_range(hsh);
-      for (auto it = range.first; it != range.second; ++it) {
-        const int j = it->second;
-        if (uns[j] == ns && memcmp(bytes, segs + (size_t)usrc[j] * MDS_SEG_DIM, nbytes) == 0) {
-          u = j;
-          break;
-        }
-      }
-      if (u < 0) {
-        u = (int)usrc.size();
-        usrc.push_back(offsets[i]);
-        uns.push_back(ns);
-        seen.emplace(hsh, u);
-      }
-      uniq_of[i] = u;
-    }
-    // blocks by piece count, in order of first appearance
-    const int nuniq = (int)usrc.size();
-    std::unordered_map<int, int> block_of;              // piece count -> block
-    std::vector<int> bcount, bns, rank((size_t)nuniq), blk((size_t)nuniq);
-    for (int u = 0; u < nuniq; ++u) {
-      auto it = block_of.find(uns[u]);
-      if (it == block_of.end()) {
-        it = block_of.emplace(uns[u], (int)bcount.size()).first;
-        bcount.push_back(0);
-        bns.push_back(uns[u]);
-      }
-      blk[u] = it->second;
-      rank[u] = bcount[it->second]++;
-    }
-    std::vector<long long> bbase(bcount.size());
-    long long acc = 0;
-    for (size_t b = 0; b < bcount.size(); ++b) {
-      bbase[b] = acc;
-      acc += (long long)bcount[b] * bns[b];
-    }
-    if (acc > 0x7fffffffll) return fail(MDS_EINVAL, "mds_set_trajectory_segments: too many segments");
-    nu = (int)acc;
-    fm.resize((size_t)MDS_SEG_DIM * nu);
-    for (int u = 0; u < nuniq; ++u) {
-      const int stride = bcount[blk[u]];
-      for (int k = 0; k < uns[u]; ++k) {
-        const double* row = segs + (size_t)(usrc[u] + k) * MDS_SEG_DIM;
-        const size_t id = (size_t)bbase[blk[u]] + rank[u] + (size_t)k * stride;
-        for (int f = 0; f < MDS_SEG_DIM; ++f) fm[(size_t)f * nu + id] = row[f];
-        // the affine map is skipped on the device when it is the identity (no RotateTrajectory above this piece)
-        bool ident = true;
-        for (int r = 0; r < 3; ++r) {
-          for (int c = 0; c < 3; ++c) ident = ident && row[27 + 3 * r + c] == (r == c ? 1.0 : 0.0);
-          ident = ident && row[36 + r] == 0.0;
-        }
-        if (!ident) fm[id] = row[0] + 8.0;               // field 0 = kind | kSegAffine
-      }
-    }
-    for (int i = 0; i < n; ++i) {
-      const int u = uniq_of[i];
-      ti[3 * i] = (int)bbase[blk[u]] + rank[u];
-      ti[3 * i + 1] = uns[u] | ((compound[i] ? 1 : 0) << 16);
-      ti[3 * i + 2] = bcount[blk[u]];
-    }
-  } catch (const std::bad_alloc&) {
-    return fail(MDS_ENOMEM, "mds_set_trajectory_segments: host allocation");
-  }
+  const char* why = "";
+  const int brc = build_traj_image(segs, offsets, compound, n, total, fm, ti, nu, &why);
+  if (brc != MDS_OK) return fail(brc, why);
   int rc = mds_set_origin(h, anchor, stream);
   if (rc != MDS_OK) return rc;
   hipError_t e = hipSuccess;

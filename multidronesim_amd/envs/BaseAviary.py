@@ -302,6 +302,14 @@ class BaseAviary:
         capi.check(self._lib.mds_set_lemniscate(self._h, capi.as_double_ptr(P), self._stream()), "mds_set_lemniscate")
         self._has_traj = True
 
+    def traj_eval(self, t: float) -> torch.Tensor:
+        """The attached trajectories sampled at ``t`` for every drone (mds_traj_eval): ``[E, D, 11]`` in the env's dtype,
+        pos3 | vel3 | acc3 | yaw | yaw_rate, world frame."""
+        self._require_open()
+        des = torch.empty((self.NUM_ENVS, self.NUM_DRONES, capi.DES_DIM), dtype=self.dtype, device=self.device)
+        capi.check(self._lib.mds_traj_eval(self._h, C.c_double(float(t)), C.c_void_p(des.data_ptr()), self._stream()), "mds_traj_eval")
+        return des
+
     def set_wind(self, force_world):
         """Constant world-frame force [N] on every drone each physics substep -- the reference's
         ``p.applyExternalForce(..., [wind_force, 0, 0], WORLD_FRAME)`` (EnvGeometric.py:463-467)."""
