@@ -1092,7 +1092,11 @@ MDS_HD void dslpid_control(const Consts<T>& c, const DslPidGains<T>& g, T ctrl_d
   const V3<T> y_ax = m_rsqrt(dot(yc, yc)) * yc;
   const V3<T> x_ax = cross(y_ax, z_ax);
   // _dslPIDAttitudeControl
-  const V3<T> cur_rpy = euler_from_quat(q);
+  // p.getEulerFromQuaternion takes the quaternion as it is given: its pitch is asin(-2 (xz - wy)), not asin(-R20) of the normalised
+  // matrix (roll and yaw are atan2 of two entries and do not see |q|).  The D term multiplies the difference by D_TOR / dt, so on an
+  // observation whose quaternion is unit only to float32 rounding the two are 1e-7 apart in the RPM.  The gimbal arms keep their pitch.
+  V3<T> cur_rpy = euler_from_quat(q);
+  if (m_abs(R.m[6]) < T(0.99999)) cur_rpy.y = m_asin(m_clamp(T(-2) * m_fma(q[0], q[2], -(q[3] * q[1])), T(-1), T(1)));
   const V3<T> r0 = col(R, 0), r1 = col(R, 1), r2 = col(R, 2);
   const V3<T> rot_e = {dot(z_ax, r1) - dot(y_ax, r2), dot(x_ax, r2) - dot(z_ax, r0), dot(y_ax, r0) - dot(x_ax, r1)};
   const T inv_dt = T(1) / ctrl_dt;

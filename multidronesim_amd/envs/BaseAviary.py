@@ -457,6 +457,23 @@ class BaseAviary:
         self.step_counter += self.PYB_STEPS_PER_CTRL
         return (self._obs, self._act) if return_action else self._obs
 
+    def dslpid_compute(self, obs, target_pos, target_rpy):
+        """DSLPIDControl.computeControlFromState for every drone on the observations given ([E,D,20]; targets [E,D,3] or [D,3]):
+        the controller of ``step_dslpid`` alone (``mds_dslpid_compute``).  It advances this env's PID memory and leaves the state
+        untouched.  Returns the RPM [E,D,4] in a tensor of its own."""
+        self._require_open()
+        def prep(a, w):
+            if not isinstance(a, torch.Tensor):
+                a = np.asarray(a, dtype=np.float64)
+                if a.shape == (self.NUM_DRONES, w):
+                    a = np.broadcast_to(a, (self.NUM_ENVS, self.NUM_DRONES, w))
+            return to_device(a, self.device, self.dtype).reshape(self.n, w)
+        ob, tp, tr = prep(obs, capi.OBS_DIM), prep(target_pos, 3), prep(target_rpy, 3)
+        rpm = torch.empty((self.NUM_ENVS, self.NUM_DRONES, capi.ACT_DIM), dtype=self.dtype, device=self.device)
+        capi.check(self._lib.mds_dslpid_compute(self._h, C.c_void_p(ob.data_ptr()), C.c_void_p(tp.data_ptr()), C.c_void_p(tr.data_ptr()),
+                                                C.c_void_p(rpm.data_ptr()), self._stream()), "mds_dslpid_compute")
+        return rpm
+
     def rollout_dslpid(self, target_pos, target_rpy, n_steps: int, first_step: int = 0, obs_every_step: bool = False):
         """``for i in range(n_steps): env.sim_step()`` of PIDEnv.py:201-207 as one C call (``mds_rollout_dslpid``).  Targets:
         [D,3] / [E,D,3] (fixed, PIDEnv's TARGET_POSITIONS) or a waypoint table [W,E,D,3] used cyclically from ``first_step``.

@@ -45,7 +45,9 @@ def test_dslpid_fused_step_matches_oracle(dtype, tol, model):
     """[UPSTREAM] DSLPIDControl (spec-level) fused with the physics step vs the oracle loop of PIDEnv.sim_step,
     halved gains, 240 Hz, 600 steps, a target change half way (the REPL's "goal" command).  CF2P only (the reference's
     default, PIDEnv.py:18): with upstream's CF2X torque formula in _dynamics the roll sign is opposite to the cf2x.urdf
-    prop layout the DSLPID mixer was written for, so DSLPID + CF2X + Physics.DYN diverges upstream too."""
+    prop layout the DSLPID mixer was written for, so DSLPID + CF2X + Physics.DYN diverges upstream too.
+    This is a closed loop judged at its end: it reaches neither integral clamp nor MIN_PWM.  The controller as an operator -- every
+    call against the oracle, every clamp, the CF2X mixer included -- is covered in tests/test_gpu_dslpid.py and tests/test_dslpid_cpu.py."""
     from oracle import np_oracle as O
     from multidronesim_amd.envs.CtrlAviary import CtrlAviary, DroneModel, Physics
     from multidronesim_amd.control.DSLPIDControl import DSLPIDControl
