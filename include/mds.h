@@ -438,8 +438,17 @@ int mds_lqr_yank_omega_compute(mds_handle* h, const void* obs_dev, const void* d
  * ThrustOmega PID of mds_thrust_omega_compute (same PID memory in the handle). */
 int mds_yank_omega_compute(mds_handle* h, const void* u_dev, const void* obs_dev, void* rpm_dev, void* stream);
 /* nominal controller of mds_step_cbf_geometric: 0 = GeometricControl(return_omegas), 1 = LQROmegaController,
- * 2 = LQRYankOmegaController (the only one valid with an order-3 CBF, and only with it) */
+ * 2 = LQRYankOmegaController (the only one valid with an order-3 CBF, and only with it), 3 = DecentralizedLQROmega
+ * (simulations/CBFTest.py:281-284, :322-324: compute(obs, skip_low_level=True), coupled over the drones of an env, the CAPPED u into
+ * the filter; MDS_ESTATE without a gain from mds_set_dlqr_omega_gain / mds_dlqr_omega_solve_gain; order 2 only).  Nominal 3 is served
+ * by mds_step_cbf_geometric and mds_rollout_cbf_geometric in their QP launch + low-level launch form; mds_rollout_cbf_geometric_fused
+ * answers MDS_EUNSUPPORTED, mds_step_nominal / mds_rollout_nominal_fused MDS_ESTATE (the unfiltered loop is mds_rollout_dlqr_omega_fused). */
 int mds_cbf_set_nominal(mds_handle* h, int which);
+/* What the filter of the last mds_step_cbf_geometric saw and gave, for tests and logs: unom_dev [n,4] = u_hat (nominal input, hover
+ * force subtracted), usafe_dev [n,4] = the filter's output (hover force not yet added back), storage type; either may be NULL.
+ * MDS_ESTATE unless that step was issued as QP launch + low-level launch (mds_cbf_last_step_kernel() == 0).  In a rollout whose
+ * low-level launch already computes the next step's nominal input, unom is the next step's. */
+int mds_cbf_get_step_inputs(mds_handle* h, void* unom_dev, void* usafe_dev, void* stream);
 /* How mds_step_cbf_geometric / mds_rollout_cbf_geometric issue a control step.  0 (default): the QP of every env in its own
  * wavefront (k_cbf_filter_gi), then low level + physics + the next step's nominal input per drone (k_lowlevel_step) -- the faster
  * form when a sizeable share of the envs iterate (C4, SURVEY 8d scene: 49 us against 60 us per control step).  1: ONE launch per
@@ -552,6 +561,8 @@ int mds_fedce_omega_init(mds_handle* h, const double V0[169], const double theta
 /* Host copies (get_thetai :72-78, P :62): theta_host [n,13,9], V_host [n,13,13]; either may be NULL.  Synchronous.  set inverts
  * every V on the host (overwrite_theta :80-85 for theta). */
 int mds_fedce_omega_get(mds_handle* h, double* theta_host, double* V_host);
+/* W_host [n,13,13] = W, the inverse the handle carries beside V: the reference's self.P after theta_update phases.  Synchronous. */
+int mds_fedce_omega_get_cov(mds_handle* h, double* W_host);
 int mds_fedce_omega_set(mds_handle* h, const double* theta_host, const double* V_host);
 /* One warm-up (EnvGeometricOmega.py:143-193) or exploration phase (:226-262) of fedCE_iteration, n_steps steps in one launch.  Per step
  * and drone: e_t = error_state(x_t, x_des) (:174-183), action = compute_low_level(u, obs) (:238-249), phi = [e_t, max(u0, 0) - M G,
@@ -560,7 +571,10 @@ int mds_fedce_omega_set(mds_handle* h, const double* theta_host, const double* V
  * covers a whole phase).  u_dev [n_steps, n, 4] float64 raw inputs; xdes_dev [n,9] float64 ([rpy, vel, pos] of x_des; NULL = zeros);
  * obs_log_dev [n_steps, n, 20] (storage type), theta_log_dev [n_steps, n, 13, 9] float64 (theta after the step) and status_dev [n]
  * int32 may be NULL.  A drone whose forward prediction does not finish (bit 0: the attempt cap, bit 1: a non-finite norm, bit 2: step
- * below 10 ulp) skips that update and has the bits or-ed into status_dev.  obs_dev [n,20]: the last observation (or NULL). */
+ * below 10 ulp) skips that update and has the bits or-ed into status_dev.  obs_dev [n,20]: the last observation (or NULL).
+ * update 3 / 4: as 1 / 2 with theta_update (:125-139, what simulations/CBFTest.py:192, :260 call), the covariance form: L = W phi /
+ * (1 + phi^T W phi), theta += L (x_tp1 - pred)^T, W = (I - L phi^T) W, not symmetrised; V += phi phi^T keeps (V, W) an inverse pair, so
+ * that phases of both forms may follow each other on one handle. */
 int mds_fedce_omega_identify(mds_handle* h, int n_steps, const double* u_dev, const double* xdes_dev, int update, void* obs_log_dev,
                              double* theta_log_dev, int32_t* status_dev, void* obs_dev, void* stream);
 /* The gain of every env (compute_controller :185-204): K_host [E, 4D, 9D] float64, uploaded in the env's dtype to the device layout

@@ -118,6 +118,7 @@ PROTOTYPES = {
     "mds_lqr_yank_omega_compute": (C.c_int, [_P, _P, _P, _P, _P]),
     "mds_yank_omega_compute": (C.c_int, [_P, _P, _P, _P, _P]),
     "mds_cbf_set_nominal": (C.c_int, [_P, C.c_int]),
+    "mds_cbf_get_step_inputs": (C.c_int, [_P, _P, _P, _P]),
     "mds_cbf_set_step_kernel": (C.c_int, [_P, C.c_int]),
     "mds_cbf_last_step_kernel": (C.c_int, [_P]),
     "mds_step_cbf_geometric": (C.c_int, [_P, C.c_double, _P, _P, _P, _P]),
@@ -136,6 +137,7 @@ PROTOTYPES = {
     "mds_fedce_omega_supported": (C.c_int, [C.POINTER(MdsConfig)]),
     "mds_fedce_omega_init": (C.c_int, [_P, _PD, _PD]),
     "mds_fedce_omega_get": (C.c_int, [_P, _PD, _PD]),
+    "mds_fedce_omega_get_cov": (C.c_int, [_P, _PD]),
     "mds_fedce_omega_set": (C.c_int, [_P, _PD, _PD]),
     "mds_fedce_omega_identify": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "mds_set_dlqr_omega_gain": (C.c_int, [_P, _PD]),

@@ -23,6 +23,8 @@ from ..._device import stream_ptr, to_device
 from ..base_controller import BaseController
 
 UPDATE_NONE, UPDATE_ALL, UPDATE_SKIP_FIRST = 0, 1, 2      # mds_fedce_omega_identify's `update`
+UPDATE_COV_ALL, UPDATE_COV_SKIP_FIRST = 3, 4              # the same two in the covariance form (theta_update)
+FORMS = ("theta_update2", "theta_update")
 
 
 class DecentralizedLQROmega(BaseController):
@@ -65,6 +67,7 @@ class DecentralizedLQROmega(BaseController):
                    "mds_fedce_omega_init")
         # a new reference object starts with fresh ThrustOmegaControllers (:70): the PID memory lives as long as this object
         capi.check(env._lib.mds_lowlevel_reset(env._h, C.c_void_p(stream_ptr(env.device))), "mds_lowlevel_reset")
+        self._form = FORMS[0]                                     # the update form of the last identify call (what P returns)
         self.K = None
         self.are_status = np.ones(self.num_envs, dtype=bool)     # False: the last compute_controller kept that env's previous K
         self.status = np.zeros((self.num_envs, D), dtype=np.int32)   # or of the identify calls' failure bits per drone (0: none)
@@ -101,7 +104,14 @@ class DecentralizedLQROmega(BaseController):
 
     @property
     def P(self):
-        """[D, 13, 13]: the information matrix V of theta_update2 (the reference's name for it, :115)."""
+        """[D, 13, 13]: what the reference's ``self.P`` holds for the update form last used by ``identify``: the information matrix V
+        after theta_update2 phases (the reference's name for it, :115), its inverse W after theta_update phases (:130, :139).  The
+        device carries both as an inverse pair through either form."""
+        if self._form == "theta_update":
+            n = self.env.n
+            W = np.zeros((n, self.mn, self.mn))
+            capi.check(self.env._lib.mds_fedce_omega_get_cov(self.env._h, capi.as_double_ptr(W)), "mds_fedce_omega_get_cov")
+            return self._one(W.reshape(self.num_envs, self.num_robots, self.mn, self.mn))
         return self._one(self._get()[1])
 
     def get_thetai(self, i):
@@ -146,12 +156,21 @@ class DecentralizedLQROmega(BaseController):
         return mean + sd * z
 
     # ------------------------------------------------------------------ the hot paths
-    def identify(self, u, x_des, update, log_obs=False, log_theta=False):
+    def identify(self, u, x_des, update, log_obs=False, log_theta=False, form="theta_update2"):
         """One warm-up or exploration phase of fedCE_iteration on the device: u [T,E,D,4] (or [T,D,4]) raw inputs, x_des [D,9] or
         [E,D,9] (reference layout [rpy, vel, pos]); ``update``: UPDATE_NONE, UPDATE_ALL or UPDATE_SKIP_FIRST (the reference's
-        `if i != 0` for a call that covers a whole phase).  Returns (obs log [T,E,D,20] or None, last obs, theta log [T,E,D,13,9] or
+        `if i != 0` for a call that covers a whole phase); ``form``: "theta_update2" (the information form, EnvGeometricOmega.py) or
+        "theta_update" (the covariance form, CBFTest.py:192, :260), which maps UPDATE_ALL / UPDATE_SKIP_FIRST to UPDATE_COV_ALL /
+        UPDATE_COV_SKIP_FIRST.  Returns (obs log [T,E,D,20] or None, last obs, theta log [T,E,D,13,9] or
         None); the failure bits of the forward prediction accumulate in ``status``."""
         env, E, D = self.env, self.num_envs, self.num_robots
+        if form not in FORMS:
+            raise ValueError(f"form must be one of {FORMS}, not {form!r}")
+        update = int(update)
+        if form == "theta_update" and update in (UPDATE_ALL, UPDATE_SKIP_FIRST):
+            update += 2
+        if update != UPDATE_NONE:
+            self._form = FORMS[update > UPDATE_SKIP_FIRST]
         u = to_device(u, env.device, torch.float64).reshape(-1, env.n, 4).contiguous()
         T = u.shape[0]
         xd = to_device(np.broadcast_to(np.asarray(x_des, dtype=np.float64), (E, D, self.m)), env.device, torch.float64)
@@ -324,7 +343,8 @@ class DecentralizedLQROmega(BaseController):
         raise NotImplementedError("theta_update2 per call is not built: identify() runs it inside the identification kernel for whole phases")
 
     def theta_update(self, phis, xtp1s):
-        raise NotImplementedError("theta_update (the covariance form) is not used by fedCE's default loop and is not built")
+        raise NotImplementedError("theta_update per call is not built: identify(form=\"theta_update\") runs it inside the identification "
+                                  "kernel for whole phases")
 
     def forward_predict(self, *a, **k):
         raise NotImplementedError("forward_predict (solve_ivp) runs inside the identification kernel (rk45_linear) and has no host entry")

@@ -158,7 +158,7 @@ struct mds_handle {
   void* ll = nullptr;            // T [6][ld]: ThrustOmega last_omega3 | integral3
   void* pid = nullptr;           // T [9][ld]: DSLPID last_rpy3 | integral_pos_e3 | integral_rpy_e3
   bool has_lqr = false;
-  int cbf_nominal = 0;           // 0 geometric, 1 lqr-omega, 2 lqr-yank-omega (order 3)
+  int cbf_nominal = 0;           // 0 geometric, 1 lqr-omega, 2 lqr-yank-omega (order 3), 3 dlqr-omega (coupled over the env's drones)
   bool has_lqr_yo = false;
   bool has_lqr12 = false;
   // device copies of the gains for the whole-rollout kernels: 0 LQR-12, 1 LQR-omega, 2 LQR-yank-omega (written by the mds_set_*_gain calls)
@@ -1733,9 +1733,11 @@ int mds_lqr_yank_omega_compute(mds_handle* h, const void* obs, const void* des, 
 }
 
 int mds_cbf_set_nominal(mds_handle* h, int which) {
-  if (!h || which < 0 || which > 2) return fail(MDS_EINVAL, "mds_cbf_set_nominal");
+  if (!h || which < 0 || which > 3) return fail(MDS_EINVAL, "mds_cbf_set_nominal");
   if (which == 1 && !h->has_lqr) return fail(MDS_ESTATE, "mds_cbf_set_nominal: call mds_set_lqr_omega_gain first");
   if (which == 2 && !h->has_lqr_yo) return fail(MDS_ESTATE, "mds_cbf_set_nominal: call mds_set_lqr_yank_omega_gain first");
+  if (which == 3 && !h->dlqr_omega_K)
+    return fail(MDS_ESTATE, "mds_cbf_set_nominal: call mds_set_dlqr_omega_gain / mds_dlqr_omega_solve_gain first");
   h->cbf_nominal = which;
   return MDS_OK;
 }
@@ -1745,6 +1747,17 @@ int mds_cbf_set_step_kernel(mds_handle* h, int one_launch) {
   h->cbf_fused = one_launch == 1;
   h->cbf_step_persistent = one_launch == 2;
   for (int k = 0; k < 3; ++k) h->next_nom_ok[k] = false;
+  return MDS_OK;
+}
+
+int mds_cbf_get_step_inputs(mds_handle* h, void* unom, void* usafe, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_cbf_get_step_inputs: null handle");
+  if (!h->cbf_unom || h->cbf_last_step_kernel != 0)
+    return fail(MDS_ESTATE, "mds_cbf_get_step_inputs: the last filtered step was not issued as QP launch + low-level launch");
+  const size_t bytes = (size_t)h->n * 4 * elem_size(h->cfg.dtype);
+  if (unom) MDS_HIP(hipMemcpyAsync(unom, h->cbf_unom, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (usafe) MDS_HIP(hipMemcpyAsync(usafe, h->cbf_usafe, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return MDS_OK;
 }
 
@@ -1877,6 +1890,16 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
       k_cbf_nominal_lqr_yo<T, T><<<grid, kBlock, 0, st>>>(params<T>(h).c, params<T>(h).lqr_yo, n_end, h->ld, t, (T)hover_sub, (const T*)h->state,
                                                           (const T*)h->lem, (const T*)obs, (T*)h->cbf_unom, (T*)h->cbf_xdes, batch0);
     });
+  } else if (h->cbf_nominal == 3) {
+    // the coupled dLQR: whole envs per workgroup (k_dlqr_omega_rollout's layout), the env range of this chain
+    const int D = h->cfg.num_drones, epb = kFedceBlock / D;
+    const dim3 grid_e((unsigned)((rg.ne + epb - 1) / epb));
+    with_dtype_no_half(h->cfg.dtype, [&](auto DT) {       // f32 / f64 (mds_set_dlqr_omega_gain refuses the rest)
+      using T = typename decltype(DT)::T;
+      k_cbf_nominal_dlqr_omega<T, T><<<grid_e, kFedceBlock, 0, st>>>(params<T>(h).c, (const T*)h->dlqr_omega_K, rg.e0, rg.e0 + rg.ne, D, h->ld, t,
+                                                                     (T)hover_sub, (const T*)h->state, (const T*)h->lem, (T*)h->cbf_unom,
+                                                                     (T*)h->cbf_xdes);
+    });
   } else {
     lowlevel(false, nullptr, 0.0, true, t, 1);
   }
@@ -1990,6 +2013,9 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
   if (!aligned16(obs) || !aligned16(obs_log)) return fail(MDS_EALIGN, "mds_rollout_cbf_geometric_fused: obs buffers");
   const int D = h->cfg.num_drones;
   const int m2 = D * (D - 1) / 2 + D * h->cbf.n_obs + 2 * D;
+  if (h->cbf_nominal == 3)
+    return fail(MDS_EUNSUPPORTED, "mds_rollout_cbf_geometric_fused: the dlqr-omega nominal couples the drones of an env and is served by "
+                                  "mds_step_cbf_geometric / mds_rollout_cbf_geometric only");
   if (h->cbf.order == 3) {
     // the order-3 loop (simulations/CBFTestOrd3.py:306-352): k_cbf_rollout_o3, one wavefront per env, steps_per_launch steps per launch
     if (!(h->cbf_nominal == 2 && h->has_lqr_yo && D <= 16 && !h->envfx && !h->cbf_hildreth && h->cfg.integrator == MDS_INTEGRATOR_EULER && !has_drag(h) &&
@@ -2400,6 +2426,16 @@ int mds_fedce_omega_get(mds_handle* h, double* theta_host, double* V_host) {
   return MDS_OK;
 }
 
+int mds_fedce_omega_get_cov(mds_handle* h, double* W_host) {
+  MDS_DEV(h);
+  if (!h || !W_host) return fail(MDS_EINVAL, "mds_fedce_omega_get_cov: null argument");
+  if (int rc = mds_fedce_supported(&h->cfg)) return rc;
+  if (!h->fo_V) return fail(MDS_ESTATE, "mds_fedce_omega_get_cov: call mds_fedce_omega_init first");
+  MDS_HIP(hipDeviceSynchronize());
+  MDS_HIP(hipMemcpy(W_host, h->fo_W, (size_t)h->n * kOmegaR * kOmegaR * sizeof(double), hipMemcpyDeviceToHost));
+  return MDS_OK;
+}
+
 int mds_fedce_omega_set(mds_handle* h, const double* theta_host, const double* V_host) {
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_fedce_omega_set: null handle");
@@ -2426,7 +2462,7 @@ int mds_fedce_omega_identify(mds_handle* h, int n_steps, const double* u_dev, co
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_fedce_omega_identify: null handle");
   if (int rc = mds_fedce_supported(&h->cfg)) return rc;
-  if (n_steps < 0 || (n_steps > 0 && !u_dev) || update < 0 || update > 2) return fail(MDS_EINVAL, "mds_fedce_omega_identify: n_steps / u_dev / update");
+  if (n_steps < 0 || (n_steps > 0 && !u_dev) || update < 0 || update > 4) return fail(MDS_EINVAL, "mds_fedce_omega_identify: n_steps / u_dev / update");
   if (!h->fo_V) return fail(MDS_ESTATE, "mds_fedce_omega_identify: call mds_fedce_omega_init first");
   if (!aligned16(obs_log_dev) || !aligned16(obs_dev) || !aligned16(theta_log_dev) || !aligned16(status_dev) || !aligned16(u_dev) ||
       !aligned16(xdes_dev))
@@ -2436,11 +2472,13 @@ int mds_fedce_omega_identify(mds_handle* h, int n_steps, const double* u_dev, co
     const dim3 grid = grid_for(h->n * 16, kFedceBlock);
     with_dtype_no_half(h->cfg.dtype, [&](auto DT) {         // f32 / f64 (mds_fedce_supported)
       using T = typename decltype(DT)::T;
-      with_flags([&](auto DRAG) {
-        k_fedce_omega_identify<T, T, DRAG()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, h->cfg.M * h->cfg.G, 1.0 / h->cfg.ctrl_freq, h->n, h->ld, n_steps,
-                                                                           (T*)h->state, (const T*)h->origin, (T*)rpm_track(h), (T*)h->ll, u_dev, xdes_dev,
-                                                                           update, h->fo_V, h->fo_W, h->fo_theta, (T*)obs_log_dev, theta_log_dev, status_dev);
-      }, has_drag(h));
+      // update 3 / 4: 1 / 2 in the covariance form (theta_update), its own instantiation; 0, 1, 2 launch what they always launched
+      with_flags([&](auto DRAG, auto COV) {
+        k_fedce_omega_identify<T, T, DRAG(), COV()><<<grid, kFedceBlock, 0, st>>>(params<T>(h).c, h->cfg.M * h->cfg.G, 1.0 / h->cfg.ctrl_freq, h->n, h->ld,
+                                                                                  n_steps, (T*)h->state, (const T*)h->origin, (T*)rpm_track(h), (T*)h->ll,
+                                                                                  u_dev, xdes_dev, update > 2 ? update - 2 : update, h->fo_V, h->fo_W,
+                                                                                  h->fo_theta, (T*)obs_log_dev, theta_log_dev, status_dev);
+      }, has_drag(h), update > 2);
     });
     MDS_HIP(hipGetLastError());
   }

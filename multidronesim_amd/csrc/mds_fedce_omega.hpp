@@ -179,6 +179,40 @@ MDS_HD int rls2_update(T* theta, T* V, T* W, const T* phi, const T* xtp1, T ctrl
   return 0;
 }
 
+// ---- rls_cov_update -------------------------------------------------------------------------------------------------------
+// theta_update (:125-139), the covariance form, for one drone, one thread.  Here the reference's P is W: L = W phi / (1 + phi^T W phi),
+// theta <- theta + L (x_tp1^T - pred^T), W <- (I - L phi^T) W = W - L (phi^T W) with theta and W taken before the update.  phi^T W is
+// the column sum, not (W phi)^T: the reference does not symmetrise.  V <- V + phi phi^T keeps (V, W) an inverse pair.  Returns
+// rk45_linear's status; non-zero leaves theta, V and W as they were.
+template <typename T, int M, int N>
+MDS_HD int rls_cov_update(T* theta, T* V, T* W, const T* phi, const T* xtp1, T ctrl_dt, int* steps, int* nfev) {
+  constexpr int R = M + N;
+  T pred[M], g[R], pw[R];
+  const LinearRhs<T, M, N> f = {theta, phi + M};
+  const int st = rk45_linear<T, M>(f, xtp1, ctrl_dt, T(1e-3), T(1e-6), pred, steps, nfev);
+  if (st) return st;
+  T s = T(1);
+  for (int r = 0; r < R; ++r) {
+    T a = T(0), b = T(0);
+    for (int k = 0; k < R; ++k) {
+      a = m_fma(W[r * R + k], phi[k], a);
+      b = m_fma(phi[k], W[k * R + r], b);
+    }
+    g[r] = a;
+    pw[r] = b;
+  }
+  for (int r = 0; r < R; ++r) s = m_fma(phi[r], g[r], s);
+  for (int r = 0; r < R; ++r) {
+    const T l = g[r] / s;
+    for (int c = 0; c < M; ++c) theta[r * M + c] = m_fma(l, xtp1[c] - pred[c], theta[r * M + c]);
+    for (int k = 0; k < R; ++k) {
+      W[r * R + k] -= l * pw[k];
+      V[r * R + k] = m_fma(phi[r], phi[k], V[r * R + k]);
+    }
+  }
+  return 0;
+}
+
 #if defined(__HIPCC__)
 // The same update with lane r of a 16-lane row owning row r of theta, V and W (rows R..15 hold zeros and stay zero).  row_sum is the
 // row's butterfly sum; phir = phi[r] (0 on the idle lanes), innov = x_tp1 - pred (the same on every lane).
@@ -196,6 +230,26 @@ __device__ __forceinline__ void rls2_update_row(const SUM& row_sum, double phir,
   for (int k = 0; k < R; ++k) {
     const double gk = __shfl(g, k, 16);
     W_row[k] -= g * (gk / s);
+    V_row[k] = fma(phir, phi[k], V_row[k]);
+  }
+}
+
+// rls_cov_update with the same split: lane r owns row r of theta, V and W (the reference's P).  (W phi)_r is local, phi^T W phi one
+// butterfly sum, (phi^T W)_c a column sum over the lanes (R butterflies; the idle lanes add zeros).
+template <int M, int N, typename SUM>
+__device__ __forceinline__ void rls_cov_update_row(const SUM& row_sum, double phir, const double* phi, const double* innov, double* th_row,
+                                                   double* V_row, double* W_row) {
+  constexpr int R = M + N;
+  double g = 0.0;
+#pragma unroll
+  for (int k = 0; k < R; ++k) g = fma(W_row[k], phi[k], g);
+  const double l = g / (1.0 + row_sum(phir * g));
+#pragma unroll
+  for (int c = 0; c < M; ++c) th_row[c] = fma(l, innov[c], th_row[c]);
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const double pw = row_sum(phir * W_row[k]);
+    W_row[k] -= l * pw;
     V_row[k] = fma(phir, phi[k], V_row[k]);
   }
 }

@@ -10,6 +10,8 @@
 //   k_dlqr_omega_rollout   : one CE phase / do_control run per launch, one drone per lane, whole envs per workgroup, error states
 //                            through LDS, the ThrustOmega PID memory in registers across the launch.
 //   k_dlqr_omega_compute   : DecentralizedLQROmega.compute(obs, skip_low_level) for every env, one call.
+//   k_cbf_nominal_dlqr_omega : the same compute(obs, skip_low_level=True) as the nominal controller of the CBF-filtered step
+//                            (simulations/CBFTest.py:303-343 with 'dlqr'), from the state planes, into the filter's scratch.
 #include <hip/hip_runtime.h>
 
 #include "mds_fedce_omega.hpp"
@@ -70,8 +72,8 @@ template <typename T> __device__ __forceinline__ void ll_store(T* __restrict__ l
 // max(u0, 0) - M G, u1..3] (computeControlFromInput clips u[0] in place, :93), the step, e_{t+1} and -- update 1: every step; 2: every
 // step but the launch's first -- rls2_update.  A drone whose forward prediction fails keeps its theta / V / W for that step and gets the
 // failure bits or-ed into status[i].  u [T,n,4] float64; xdes [n,9] float64 (NULL: zeros); obs_log [T,n,20] S, theta_log [T,n,13,9]
-// float64 and status [n] may be NULL.
-template <typename T, typename S, bool DRAG>
+// float64 and status [n] may be NULL.  COV: the update is theta_update, the covariance form (simulations/CBFTest.py:192, :260), rls_cov_update_row.
+template <typename T, typename S, bool DRAG, bool COV = false>
 __global__ __launch_bounds__(kFedceBlock) void k_fedce_omega_identify(const Consts<T> c, const double mg, const double ctrl_dt, const int n,
                                                                       const size_t ld, const int n_steps, S* __restrict__ state,
                                                                       const T* __restrict__ origin, T* __restrict__ last_rpm,
@@ -127,7 +129,8 @@ __global__ __launch_bounds__(kFedceBlock) void k_fedce_omega_identify(const Cons
       if (st == 0) {
         double innov[M];
         for (int k = 0; k < M; ++k) innov[k] = e1[k] - pred[k];
-        rls2_update_row<M, N>(RowSum16{}, lane_pick<R>(phi, r), phi, innov, th, Vrow, Wrow);
+        if (COV) rls_cov_update_row<M, N>(RowSum16{}, lane_pick<R>(phi, r), phi, innov, th, Vrow, Wrow);
+        else rls2_update_row<M, N>(RowSum16{}, lane_pick<R>(phi, r), phi, innov, th, Vrow, Wrow);
       } else {
         bits |= st;
       }
@@ -293,6 +296,51 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_omega_compute(const Consts
       u[0] = m_clamp(u[0], T(4) * c.min_motor_thrust, c.max_motor_thrust);       // cap_u (:233-236), after the action is made
       store4<S, T>(u_out + i * 4, u);
     }
+  }
+}
+
+// The nominal controller of the CBF-filtered step with 'dlqr' (simulations/CBFTest.py:303-343): ctrl[0].compute(obs, skip_low_level=True)
+// for the envs [e0, e_end) from the state planes (Lemniscates only, like every nominal of that step).  Per drone: trajectory sample ->
+// error_state9 against [0, 0, yaw, vel, pos] -> u = -sum_k K e_k in drone order + (M G, 0, 0, 0) -> cap_u, whose output is what the script
+// feeds the filter (:323-324, unlike the unfiltered loop's low level) -> u_hat = (u0 - hover_sub, u1..3) [n,4] and xdes [n,9] into the
+// scratch planes the QP and k_lowlevel_step read.  The layout is k_dlqr_omega_rollout's: 256 / D whole envs per workgroup.
+template <typename T, typename S>
+__global__ __launch_bounds__(kFedceBlock) void k_cbf_nominal_dlqr_omega(const Consts<T> c, const T* __restrict__ K, const int e0,
+                                                                        const int e_end, const int D, const size_t ld, const double t,
+                                                                        const T hover_sub, const S* __restrict__ state,
+                                                                        const T* __restrict__ lem, S* __restrict__ unom,
+                                                                        S* __restrict__ xdes) {
+  constexpr int M = kOmegaM;
+  __shared__ T se[kFedceBlock][M];
+  const int epb = kFedceBlock / D;
+  const int le = threadIdx.x / D, j = threadIdx.x - le * D;
+  const size_t env = (size_t)e0 + (size_t)blockIdx.x * epb + le;
+  const bool valid = le < epb && env < (size_t)e_end;
+  const size_t i = env * D + j;
+  Desired<T> des = {};
+  LemniscateParams<T> P = {};
+  if (valid) {
+    State<T> s;
+    load_state<S, T>(state, ld, i, s);
+    P = {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)], lem[lidx(5, i, ld)],
+         lem[lidx(6, i, ld)]};
+    des = lemniscate_local(P, t);
+    T e[M];
+    error_state9<T>(euler_from_quat(s.q), s.v, s.p - des.p, des.v, des.yaw, e);
+    for (int k = 0; k < M; ++k) se[threadIdx.x][k] = e[k];
+  }
+  __syncthreads();
+  if (valid) {
+    T u[4];
+    dlqr_input_m<T, M>(K, env, D, j, se + le * D, u);
+    u[0] += c.gravity;
+    u[0] = m_clamp(u[0], T(4) * c.min_motor_thrust, c.max_motor_thrust);         // cap_u (:233-236)
+    u[0] -= hover_sub;
+    store4<S, T>(unom + i * 4, u);
+    S* xd = xdes + i * 9;
+    xd[0] = (S)0; xd[1] = (S)0; xd[2] = (S)des.yaw;
+    xd[3] = (S)des.v.x; xd[4] = (S)des.v.y; xd[5] = (S)des.v.z;
+    xd[6] = (S)(des.p.x + P.cx); xd[7] = (S)(des.p.y + P.cy); xd[8] = (S)(des.p.z + P.cz);
   }
 }
 

@@ -497,9 +497,10 @@ class BaseAviary:
 
     def set_cbf_nominal(self, which: str):
         """Nominal controller of ``step_cbf_geometric``: "geometric" (GeometricControl return_omegas),
-        "lqr_omega" (LQROmegaController) or "lqr_yank_omega" (LQRYankOmegaController, the order-3 loop of
-        simulations/CBFTestOrd3.py); the LQR ones need a controller constructed on this env first."""
-        capi.check(self._lib.mds_cbf_set_nominal(self._h, {"geometric": 0, "lqr_omega": 1, "lqr_yank_omega": 2}[which]),
+        "lqr_omega" (LQROmegaController), "lqr_yank_omega" (LQRYankOmegaController, the order-3 loop of
+        simulations/CBFTestOrd3.py) or "dlqr_omega" (DecentralizedLQROmega, coupled over the drones of an env; order 2, the step loop
+        only); the LQR ones need a controller constructed on this env first, "dlqr_omega" an uploaded gain."""
+        capi.check(self._lib.mds_cbf_set_nominal(self._h, {"geometric": 0, "lqr_omega": 1, "lqr_yank_omega": 2, "dlqr_omega": 3}[which]),
                    "mds_cbf_set_nominal")
 
     def set_cbf_step_kernel(self, one_launch):
@@ -509,6 +510,15 @@ class BaseAviary:
         ``rollout_cbf_geometric`` then runs 25 steps per launch)."""
         mode = 2 if one_launch == "persistent" else int(one_launch)
         capi.check(self._lib.mds_cbf_set_step_kernel(self._h, C.c_int(mode)), "mds_cbf_set_step_kernel")
+
+    def cbf_step_inputs(self):
+        """(u_hat, u_safe) [E, D, 4] of the last ``step_cbf_geometric``: the nominal input as the filter saw it and the filter's
+        output, both without the hover force (mds_cbf_get_step_inputs; the QP launch + low-level launch form only)."""
+        self._require_open()
+        u = torch.empty((2, self.NUM_ENVS, self.NUM_DRONES, 4), dtype=self.dtype, device=self.device)
+        capi.check(self._lib.mds_cbf_get_step_inputs(self._h, C.c_void_p(u[0].data_ptr()), C.c_void_p(u[1].data_ptr()), self._stream()),
+                   "mds_cbf_get_step_inputs")
+        return u[0], u[1]
 
     def cbf_last_step_kernel(self) -> int:
         """2: the most recent CBF-filtered step ran in the several-steps-per-launch kernel, 1: as one launch, 0: as QP launch +
