@@ -194,6 +194,19 @@ int mds_traj_eval(mds_handle* h, double t, void* des_dev, void* stream);
 /* trajectories/Lemniscate.py:14-30: one Lemniscate per drone, params_host double [n,7] =
  * (a, omega, centre_x, centre_y, centre_z, yaw_rate, phase_shift). */
 int mds_set_lemniscate(mds_handle* h, const double* params_host, void* stream);
+/* YAW-FREE HANDLES.  Every upload scans the yaw_rate column: where every drone's is +-0 (the class default of the reference's
+ * Lemniscate, and what all its flight scripts use) the handle is yaw-free -- mds_traj_yaw_free returns 1 -- and mds_step_geometric,
+ * mds_rollout_geometric and mds_rollout_geometric_fused (GeometricControl; both launch forms, every dtype and integrator) run kernels
+ * that do not form the controller's products with the desired yaw, the zero yaw rate and the zero z components of the planar
+ * trajectory.  One drone with a yaw rate, or segment tables, clear the flag; the next upload decides anew.  The decision is the
+ * handle's: every kernel that serves it takes the same form, so launch forms, ragged and aligned shards agree as before.
+ * Contract: for finite states the results are equal (==) to the general kernels', and the same bits unless a sum that lost a zero
+ * term is itself exactly zero -- the only possible difference is the sign of a zero.  For a state that is not finite the general
+ * form returns NaN throughout (inf * 0), the yaw-free form may not.  The LQR controllers, the CBF loops, ground effect / downwash
+ * and the stand-alone conversions always run the general form.
+ * mds_set_traj_specialisation(h, 0) keeps a handle on the general kernels (default 1; tests compare the two). */
+int mds_traj_yaw_free(mds_handle* h);
+int mds_set_traj_specialisation(mds_handle* h, int on);
 int mds_set_geometric_gains(mds_handle* h, const mds_geometric_gains* gains);
 
 /* One fused control step of simulations/EnvGeometric.py:434-469 for every drone:

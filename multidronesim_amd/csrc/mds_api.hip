@@ -118,6 +118,8 @@ struct mds_handle {
   double* init_pose = nullptr;   // double [n*6]: xyz, rpy of the last mds_reset (episode resets on the device, mds_reset_async)
   bool has_traj = false;
   int traj_mode = 0;             // 1: per-drone Lemniscate planes (fused fp32 fast path), 2: general segment tables
+  bool traj_yaw_free = false;    // every Lemniscate of the last upload has yaw_rate = +-0 (mds_set_lemniscate; segment tables: false)
+  bool traj_spec = true;         // mds_set_traj_specialisation: such a handle steps through the yaw-free kernels
   double* segs = nullptr;        // device [MDS_SEG_DIM, total]: field-major (mds_traj.hpp SegTable)
   int nseg_total = 0;
   int* tinfo = nullptr;          // device [n, 3] = first segment, nseg | compound << 16, stride between pieces (mds_traj.hpp TrajInfo)
@@ -787,8 +789,11 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   // re-base the local frame onto the trajectory centres (host gathers them from params)
   double* centres = new (std::nothrow) double[(size_t)n * 3];
   if (!centres) return fail(MDS_ENOMEM, "mds_set_lemniscate: host allocation");
-  for (int i = 0; i < n; ++i)
+  bool yaw_free = true;          // decided per upload, for the whole handle: every kernel that serves it then takes the same form
+  for (int i = 0; i < n; ++i) {
     for (int k = 0; k < 3; ++k) centres[(size_t)3 * i + k] = params[(size_t)7 * i + 2 + k];
+    yaw_free = yaw_free && params[(size_t)7 * i + 5] == 0.0;
+  }
   int rc = mds_set_origin(h, centres, stream);
   delete[] centres;
   if (rc != MDS_OK) return rc;
@@ -801,8 +806,20 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   MDS_HIP(hipStreamSynchronize(st));
   h->has_traj = true;
   h->traj_mode = 1;
+  h->traj_yaw_free = yaw_free;
   return MDS_OK;
 }
+
+int mds_traj_yaw_free(mds_handle* h) { return h && h->traj_yaw_free ? 1 : 0; }
+
+int mds_set_traj_specialisation(mds_handle* h, int on) {
+  if (!h) return fail(MDS_EINVAL, "mds_set_traj_specialisation: null handle");
+  h->traj_spec = on != 0;
+  return MDS_OK;
+}
+
+// the fused GeometricControl step and the whole-rollout kernel take the yaw-free form together (both launch forms, every dtype)
+static bool use_yaw_free(const mds_handle* h) { return h->traj_mode == 1 && h->traj_yaw_free && h->traj_spec; }
 
 int mds_set_trajectory_segments(mds_handle* h, const double* segs, const int32_t* offsets, const int32_t* compound,
                                 const double* anchor, int32_t total, void* stream) {
@@ -830,6 +847,7 @@ int mds_set_trajectory_segments(mds_handle* h, const double* segs, const int32_t
   h->nseg_total = nu;
   h->has_traj = true;
   h->traj_mode = 2;
+  h->traj_yaw_free = false;
   return MDS_OK;
 }
 
@@ -883,14 +901,15 @@ static int launch_step_geometric(mds_handle* h, double t, void* obs, void* act, 
     }, rk4, drag);
     return MDS_OK;
   }
-  with_flags([&](auto HAS_OBS, auto HAS_ACT, auto RK4, auto DRAG) {
+  with_flags([&](auto Y0, auto HAS_OBS, auto HAS_ACT, auto RK4, auto DRAG) {
     with_dtype(h->cfg.dtype, [&](auto DT) {
       using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
-      k_step_geometric<T, S, HAS_OBS(), HAS_ACT(), RK4(), DRAG(), DT.COMP><<<grid, kBlock, pad, st>>>(params<T>(h).c, h->n, h->ld, t, (S*)h->state,
-                                                                                                      (const T*)h->lem, (T*)rpm_track(h), (S*)obs,
-                                                                                                      (S*)act, (int)batch0, (S*)h->state_lo);
+      auto* const k = Y0() ? &k_step_geometric_y0<T, S, HAS_OBS(), HAS_ACT(), RK4(), DRAG(), DT.COMP>
+                           : &k_step_geometric<T, S, HAS_OBS(), HAS_ACT(), RK4(), DRAG(), DT.COMP>;
+      k<<<grid, kBlock, pad, st>>>(params<T>(h).c, h->n, h->ld, t, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs, (S*)act, (int)batch0,
+                                   (S*)h->state_lo);
     });
-  }, obs != nullptr, act != nullptr, rk4, drag);
+  }, use_yaw_free(h), obs != nullptr, act != nullptr, rk4, drag);
   return MDS_OK;
 }
 
@@ -928,9 +947,11 @@ static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_step
                 params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->origin, SegTable{h->segs, h->nseg_total}, h->tinfo,
                 (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last, (S*)h->state_lo);
         } else {
-          k_rollout_geometric<T, S, RK4(), DRAG(), CTRL(), COMP, OBS()><<<grid, kBlock, 0, st>>>(
-              params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs_log, log_stride,
-              (S*)obs_last, (T*)h->ll, (const S*)obs_last, (S*)h->state_lo);
+          auto* k = &k_rollout_geometric<T, S, RK4(), DRAG(), CTRL(), COMP, OBS()>;
+          if constexpr (CTRL() == 0)
+            if (use_yaw_free(h)) k = &k_rollout_geometric_y0<T, S, RK4(), DRAG(), COMP, OBS()>;
+          k<<<grid, kBlock, 0, st>>>(params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs_log,
+                                     log_stride, (S*)obs_last, (T*)h->ll, (const S*)obs_last, (S*)h->state_lo);
         }
       };
       // The kernels take the compensated storage (COMP: MDS_F32C handles) and the destination of the rows (OBS) as template arguments.  The

@@ -554,7 +554,8 @@ __device__ __forceinline__ void load_geo_in(const S* __restrict__ state, const T
 }
 
 // One batch row of the fused kernel: controller + physics on registers already loaded.
-template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP = false>
+// Y0: the yaw-free form of the trajectory and the controller (mds_math.hpp), for handles whose Lemniscates were uploaded without yaw.
+template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP = false, bool Y0 = false>
 __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, const size_t ld, const double t, const int i,
                                             GeoIn<T>& in, S* __restrict__ state, T* __restrict__ last_rpm,
                                             S* __restrict__ obs, S* __restrict__ action_out, unsigned char* lds,
@@ -568,10 +569,10 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
     if (DRAG)
       for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
     {
-      const Desired<T> des = lemniscate_local(P, t);
+      const Desired<T> des = lemniscate_local<T, Y0>(P, t);
       const Frame<T> F = make_frame(s.q, s.w);
       T u[4];
-      geometric_control<T>(c, s.p - des.p, F.R, s.v, F.av, des, u, nullptr);
+      geometric_control<T, Y0>(c, s.p - des.p, F.R, s.v, F.av, des, u, nullptr);
       input_to_action(c, u, act);
       if (COMP) aviary_step_comp<T, RK4, DRAG>(c, s, in.r, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, s, F, act, prev, clipped);
@@ -591,13 +592,12 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
 
 // One batch of 256 drones per workgroup, inputs loaded straight into registers; every dtype / integrator / physics
 // combination is an instantiation of this kernel (the fp32 / Euler / DYN one is the bench's hot kernel).
-template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP = false>
-__global__ __launch_bounds__(kBlock, 1) void k_step_geometric(const Consts<T> c, const int n, const size_t ld, const double t,
-                                                           S* __restrict__ state, const T* __restrict__ lem,
-                                                           T* __restrict__ last_rpm, S* __restrict__ obs,
-                                                           S* __restrict__ action_out, const int batch0,
-                                                           S* __restrict__ state_lo = nullptr) {
-  __shared__ __align__(16) unsigned char lds[HAS_OBS ? (kBlock * kObsDim * sizeof(S)) : 16];
+// The body of both entry points (k_step_geometric: Y0 false, the general form; k_step_geometric_y0: the yaw-free form).
+template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP, bool Y0>
+__device__ __forceinline__ void step_geometric_body(unsigned char* lds, const Consts<T>& c, const int n, const size_t ld, const double t,
+                                                    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm,
+                                                    S* __restrict__ obs, S* __restrict__ action_out, const int batch0,
+                                                    S* __restrict__ state_lo) {
   // batch0: first 256-drone batch of this launch (a rollout may step the two halves of the shard on two streams)
   const int i = (batch0 + blockIdx.x) * kBlock + threadIdx.x;
   GeoIn<T> in;
@@ -605,7 +605,27 @@ __global__ __launch_bounds__(kBlock, 1) void k_step_geometric(const Consts<T> c,
     load_geo_in<T, S>(state, lem, ld, i, in);
     if (COMP) load_resid<S, T>(state_lo, ld, i, in.r);
   }
-  geo_process<T, S, HAS_OBS, HAS_ACT, RK4, DRAG, COMP>(c, n, ld, t, i, in, state, last_rpm, obs, action_out, lds, state_lo);
+  geo_process<T, S, HAS_OBS, HAS_ACT, RK4, DRAG, COMP, Y0>(c, n, ld, t, i, in, state, last_rpm, obs, action_out, lds, state_lo);
+}
+template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP = false>
+__global__ __launch_bounds__(kBlock, 1) void k_step_geometric(const Consts<T> c, const int n, const size_t ld, const double t,
+                                                           S* __restrict__ state, const T* __restrict__ lem,
+                                                           T* __restrict__ last_rpm, S* __restrict__ obs,
+                                                           S* __restrict__ action_out, const int batch0,
+                                                           S* __restrict__ state_lo = nullptr) {
+  __shared__ __align__(16) unsigned char lds[HAS_OBS ? (kBlock * kObsDim * sizeof(S)) : 16];
+  step_geometric_body<T, S, HAS_OBS, HAS_ACT, RK4, DRAG, COMP, false>(lds, c, n, ld, t, state, lem, last_rpm, obs, action_out, batch0, state_lo);
+}
+// The same kernel in the yaw-free form: what the library launches for a handle whose Lemniscates all have yaw_rate = 0
+// (mds_traj_yaw_free).  An entry point of its own, same arguments.
+template <typename T, typename S, bool HAS_OBS, bool HAS_ACT, bool RK4, bool DRAG, bool COMP = false>
+__global__ __launch_bounds__(kBlock, 1) void k_step_geometric_y0(const Consts<T> c, const int n, const size_t ld, const double t,
+                                                              S* __restrict__ state, const T* __restrict__ lem,
+                                                              T* __restrict__ last_rpm, S* __restrict__ obs,
+                                                              S* __restrict__ action_out, const int batch0,
+                                                              S* __restrict__ state_lo = nullptr) {
+  __shared__ __align__(16) unsigned char lds[HAS_OBS ? (kBlock * kObsDim * sizeof(S)) : 16];
+  step_geometric_body<T, S, HAS_OBS, HAS_ACT, RK4, DRAG, COMP, true>(lds, c, n, ld, t, state, lem, last_rpm, obs, action_out, batch0, state_lo);
 }
 
 // ------------------------------------------------------------------------------------
@@ -755,12 +775,15 @@ constexpr int kObsLast = 0, kObsInPlace = 1, kObsLog = 2;
 template <typename T, bool RK4, bool DRAG, int CTRL, int COMP, int OBS> constexpr int rollout_min_waves() {
   return !(sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0 && COMP == 0) ? 1 : (OBS == kObsInPlace || OBS == kObsLog) ? 6 : OBS == kObsLast ? 5 : 1;
 }
-template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0, int COMP = -1, int OBS = -1>
-__global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP, OBS>())) void k_rollout_geometric(
-    const Consts<T> c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt, const int n_steps,
-    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
-    S* __restrict__ obs_last, T* __restrict__ ll = nullptr, const S* __restrict__ obs_prev = nullptr, S* __restrict__ state_lo = nullptr) {
-  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+// The loop is the body of two entry points: k_rollout_geometric (Y0 false: the general form) and, for CTRL 0, k_rollout_geometric_y0 (the
+// yaw-free form of the trajectory and the controller, mds_math.hpp: what the library launches for a handle whose Lemniscates all have
+// yaw_rate = 0).  c_arg must be the kernel's first argument (the lean loops read the constants through the kernarg segment).
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP, int OBS, bool Y0>
+__device__ __forceinline__ void rollout_geometric_body(
+    unsigned char* lds, const Consts<T>& c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt,
+    const int n_steps, S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log,
+    const size_t log_stride, S* __restrict__ obs_last, T* __restrict__ ll, const S* __restrict__ obs_prev, S* __restrict__ state_lo) {
+  static_assert(!Y0 || CTRL == 0, "the yaw-free form is GeometricControl's");
   const bool comp = COMP < 0 ? state_lo != nullptr : COMP != 0;
   const int omode = OBS < 0 ? (obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog) : OBS;
   // re-forming the loop's invariants per step pays where the register budget decides (Euler, plain storage: fp32 125 -> 71 VGPRs,
@@ -815,9 +838,9 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
       // (per-lane parameters: what lemniscate_local derives from them is formed here every step, not held across the loop)
       if (kLean) {
         MDS_KEEP_V(in.P.a);
-        MDS_KEEP_V(in.P.yaw_rate);
+        if (!Y0) MDS_KEEP_V(in.P.yaw_rate);
       }
-      const Desired<T> des = lemniscate_local(in.P, t);
+      const Desired<T> des = lemniscate_local<T, Y0>(in.P, t);
       T u[4];
       if (CTRL == 0) {
         if (!kCarry) {
@@ -826,7 +849,7 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
           MDS_KEEP_V(F.r22m1);
           F.R.m[8] = T(1) + F.r22m1;
         }
-        geometric_control<T>(c, in.s.p - des.p, F.R, in.s.v, F.av, des, u, nullptr);
+        geometric_control<T, Y0>(c, in.s.p - des.p, F.R, in.s.v, F.av, des, u, nullptr);
       } else if (CTRL == 1) {
         lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(in.s.q), quat_rotate(in.s.q, in.s.w), in.s.v, in.s.p - des.p,
                          des.v, des.yaw, des.yaw_rate, u);
@@ -873,6 +896,25 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP
       ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
     }
   }
+}
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0, int COMP = -1, int OBS = -1>
+__global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, CTRL, COMP, OBS>())) void k_rollout_geometric(
+    const Consts<T> c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt, const int n_steps,
+    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
+    S* __restrict__ obs_last, T* __restrict__ ll = nullptr, const S* __restrict__ obs_prev = nullptr, S* __restrict__ state_lo = nullptr) {
+  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  rollout_geometric_body<T, S, RK4, DRAG, CTRL, COMP, OBS, false>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm, obs_log,
+                                                                  log_stride, obs_last, ll, obs_prev, state_lo);
+}
+// GeometricControl's loop in the yaw-free form: an entry point of its own, same arguments (Kp, ll and obs_prev are not read).
+template <typename T, typename S, bool RK4, bool DRAG, int COMP = -1, int OBS = -1>
+__global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, 0, COMP, OBS>())) void k_rollout_geometric_y0(
+    const Consts<T> c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt, const int n_steps,
+    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
+    S* __restrict__ obs_last, T* __restrict__ ll = nullptr, const S* __restrict__ obs_prev = nullptr, S* __restrict__ state_lo = nullptr) {
+  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  rollout_geometric_body<T, S, RK4, DRAG, 0, COMP, OBS, true>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm, obs_log,
+                                                              log_stride, obs_last, ll, obs_prev, state_lo);
 }
 
 // The same whole-rollout loop for general trajectories (segment tables, evaluated in double every step like k_step_traj).

@@ -46,6 +46,19 @@ MDS_HD double m_sqrt(double x) { return sqrt(x); }
 MDS_HD double m_rsqrt(double x) { return 1.0 / sqrt(x); }
 MDS_HD float m_fma(float a, float b, float c) { return fmaf(a, b, c); }
 MDS_HD double m_fma(double a, double b, double c) { return fma(a, b, c); }
+// a * b rounded on its own, for a product that feeds a plain sum and must not be contracted into it (the yaw-free controller form: the
+// general form rounds these products first, inside a cross product whose other term is a literal zero).  The product goes through an
+// empty asm the optimiser cannot look through: switching contraction off for the multiplication alone is not enough, a negation
+// folded into it hands the product the negation's flags (-(a * b) - c became fma(-a, b, -c) on the device).
+template <typename T> MDS_HD T m_mul_rn(T a, T b) {
+  T r = a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(r));
+#else
+  asm("" : "+m"(r));
+#endif
+  return r;
+}
 MDS_HD float m_rint(float x) { return rintf(x); }
 MDS_HD double m_rint(double x) { return rint(x); }
 MDS_HD float m_exp(float x) { return expf(x); }
@@ -783,7 +796,9 @@ template <typename T> struct Desired {
 template <typename T> struct LemniscateParams {
   T a, omega, cx, cy, cz, yaw_rate, phase_shift;
 };
-template <typename T> MDS_HD Desired<T> lemniscate_local(const LemniscateParams<T>& P, double t) {
+// Y0 (yaw-free form): for a trajectory uploaded with yaw_rate = +-0 -- the library decides per handle, mds_set_lemniscate -- the yaw
+// block is not formed: yaw = yaw_rate = +0, what the general form returns there up to the sign of yaw_rate's zero.
+template <typename T, bool Y0 = false> MDS_HD Desired<T> lemniscate_local(const LemniscateParams<T>& P, double t) {
   Desired<T> d;
   const T th = reduced_phase<T>(t, P.omega, P.phase_shift);
   T s, c;
@@ -801,6 +816,10 @@ template <typename T> MDS_HD Desired<T> lemniscate_local(const LemniscateParams<
   const T inv3 = T(-0.125) * (inv2 * inv);
   const T aw2 = aw * P.omega;
   d.a = {T(4) * aw2 * sin2 * (T(3) * cos2 + T(7)) * inv3, aw2 * c * (T(44) * cos2 + cos4 - T(21)) * inv3, T(0)};
+  if (Y0) {
+    d.yaw = d.yaw_rate = T(0);
+    return d;
+  }
   T sy = T(0), cy = T(1);
   if (P.yaw_rate != T(0)) {   // sin 0 = 0, cos 0 = 1 exactly: skipping is bitwise neutral, and wave-uniform in C2/C3
     const T ph = reduced_phase<T>(t, P.yaw_rate, T(0));
@@ -846,16 +865,34 @@ template <typename T> struct GeoAux {  // return_omegas=True outputs (:106-108)
   V3<T> w_des;
   V3<T> b1d, b2d, b3d;  // columns of R_des
 };
-template <typename T>
+//
+// Y0, the yaw-free form: for a planar desired state without yaw (des.v.z = des.a.z = 0, des.yaw = des.yaw_rate = 0: what
+// lemniscate_local<T, true> returns; the fields themselves are not read).  With b1c = (1, 0, 0) and b1c_dot = 0 the products by these
+// zeros, by the 1 and the sums with them are not formed; every operation that remains has the form, the association and the rounding
+// of the general one (a product the general form rounds before a zero term is added to it stays a product rounded on its own:
+// m_mul_rn where a plain sum reads it, an FMA operand elsewhere).  For a finite state the outputs are == the general form's at
+// yaw_rate = +-0, and the same bits unless a sum that lost a zero term is itself exactly zero (x*0 + (-0) is +0, -0 alone is not);
+// where the state is not finite the general form returns NaN throughout (x*0 is NaN for x = inf), this one may not.  DESIGN.md section 4
+// has the argument term by term.
+template <typename T, bool Y0 = false>
 MDS_HD void geometric_control(const Consts<T>& c, V3<T> p_rel, const M3<T>& R, V3<T> v_world, V3<T> w,
                               const Desired<T>& des, T u[4], GeoAux<T>* aux) {
   const V3<T> Kp = {c.kp[0], c.kp[1], c.kp[2]}, Kv = {c.kv[0], c.kv[1], c.kv[2]};
   const V3<T> v_b = mulT(R, v_world);                                   // :70
-  const V3<T> RTvd = mulT(R, des.v);
+  V3<T> RTvd, tw;
+  if (Y0) {                                                             // des.v.z = 0: the third product of each row is not formed
+    RTvd = {m_fma(R.m[0], des.v.x, R.m[3] * des.v.y), m_fma(R.m[1], des.v.x, R.m[4] * des.v.y), m_fma(R.m[2], des.v.x, R.m[5] * des.v.y)};
+  } else {
+    RTvd = mulT(R, des.v);
+  }
   const V3<T> ev = v_b - RTvd;
   // f_des_body/m = R^T(g e3 - Kp ep + a_d) - Kv ev - w x R^T v_d      (:73-74)
-  V3<T> tw = des.a - hadamard(Kp, p_rel);
-  tw.z += c.g_ctrl;
+  if (Y0) {                                                             // des.a.z = 0: (0 - x) + g = g - x, x rounded first
+    tw = {des.a.x - Kp.x * p_rel.x, des.a.y - Kp.y * p_rel.y, c.g_ctrl - m_mul_rn(Kp.z, p_rel.z)};
+  } else {
+    tw = des.a - hadamard(Kp, p_rel);
+    tw.z += c.g_ctrl;
+  }
   const V3<T> fb_m = mulT(R, tw) - hadamard(Kv, ev) - cross(w, RTvd);
   V3<T> f_w = mul(R, c.mass * fb_m);                                    // :75
   T f2 = dot(f_w, f_w);
@@ -868,24 +905,43 @@ MDS_HD void geometric_control(const Consts<T>& c, V3<T> p_rel, const M3<T>& R, V
     inv_fn = m_rsqrt(f2);
   }
   const T fbz = dot(col(R, 2), f_w);                                    // (R^T f_w).z  (:85)
-  T sy = T(0), cy = T(1);
-  if (des.yaw != T(0)) m_sincos(des.yaw, &sy, &cy);                     // exact at 0, skipped when the whole wave has yaw 0
-  const V3<T> b1c = {cy, sy, T(0)};                                     // :88
   const V3<T> b3d = inv_fn * f_w;
-  const V3<T> c1 = cross(b3d, b1c);
-  const T inv_n1 = m_rsqrt(dot(c1, c1));
-  const V3<T> b2d = inv_n1 * c1;
-  const V3<T> b1d = cross(b2d, b3d);                                    // :91; orthonormal b2d, b3d: already a unit vector
-  const V3<T> b1c_dot = {-sy * des.yaw_rate, cy * des.yaw_rate, T(0)};  // :95
-  const V3<T> f_dot = (c.mass * inv_fn) * mul(R, hadamard(Kp, ev));     // :96
-  const V3<T> b3d_dot = reject(f_dot, b3d);                             // :97
-  const V3<T> inner = inv_n1 * (cross(b1c_dot, b3d) + cross(b1c, b3d_dot));       // |b1c x b3d| = |b3d x b1c|
-  const V3<T> b2d_dot = reject(inner, b2d);                             // :98-99
-  const V3<T> b1d_dot = cross(b3d_dot, b2d) + cross(b3d, b2d_dot);      // :100
-  // W = R_des @ R_dot_des (no-op transpose, :102); w_des = (W21, W02, W10) (:103)
-  const V3<T> w_des = {m_fma(b1d.z, b2d_dot.x, m_fma(b2d.z, b2d_dot.y, b3d.z * b2d_dot.z)),
-                       m_fma(b1d.x, b3d_dot.x, m_fma(b2d.x, b3d_dot.y, b3d.x * b3d_dot.z)),
-                       m_fma(b1d.y, b1d_dot.x, m_fma(b2d.y, b1d_dot.y, b3d.y * b1d_dot.z))};
+  V3<T> b1d, b2d, w_des;
+  if (Y0) {
+    // b1c = (1, 0, 0), b1c_dot = 0: c1 = b3d x b1c = (0, b3d.z, -b3d.y), so b2d.x, inner.x and b2d_dot.x are zero
+    const T inv_n1 = m_rsqrt(m_fma(b3d.z, b3d.z, b3d.y * b3d.y));
+    b2d = {T(0), inv_n1 * b3d.z, inv_n1 * -b3d.y};
+    b1d = {m_fma(b2d.y, b3d.z, -(b2d.z * b3d.y)), b2d.z * b3d.x, -(b2d.y * b3d.x)};
+    const V3<T> f_dot = (c.mass * inv_fn) * mul(R, hadamard(Kp, ev));   // :96
+    const V3<T> b3d_dot = reject(f_dot, b3d);                           // :97
+    const T inner_y = inv_n1 * -b3d_dot.z, inner_z = inv_n1 * b3d_dot.y;          // b1c x b3d_dot = (0, -b3d_dot.z, b3d_dot.y)
+    const T d = -m_fma(b2d.y, inner_y, b2d.z * inner_z);
+    const T b2d_dot_y = m_fma(d, b2d.y, inner_y), b2d_dot_z = m_fma(d, b2d.z, inner_z);
+    // b1d_dot: in y and z each cross product is down to one rounded product, and the two are then added
+    const V3<T> b1d_dot = {m_fma(b3d_dot.y, b2d.z, -(b3d_dot.z * b2d.y)) + m_fma(b3d.y, b2d_dot_z, -(b3d.z * b2d_dot_y)),
+                           -m_mul_rn(b3d_dot.x, b2d.z) - m_mul_rn(b3d.x, b2d_dot_z),
+                           m_mul_rn(b3d_dot.x, b2d.y) + m_mul_rn(b3d.x, b2d_dot_y)};
+    w_des = {m_fma(b2d.z, b2d_dot_y, b3d.z * b2d_dot_z), m_fma(b1d.x, b3d_dot.x, b3d.x * b3d_dot.z),
+             m_fma(b1d.y, b1d_dot.x, m_fma(b2d.y, b1d_dot.y, b3d.y * b1d_dot.z))};
+  } else {
+    T sy = T(0), cy = T(1);
+    if (des.yaw != T(0)) m_sincos(des.yaw, &sy, &cy);                   // exact at 0, skipped when the whole wave has yaw 0
+    const V3<T> b1c = {cy, sy, T(0)};                                   // :88
+    const V3<T> c1 = cross(b3d, b1c);
+    const T inv_n1 = m_rsqrt(dot(c1, c1));
+    b2d = inv_n1 * c1;
+    b1d = cross(b2d, b3d);                                              // :91; orthonormal b2d, b3d: already a unit vector
+    const V3<T> b1c_dot = {-sy * des.yaw_rate, cy * des.yaw_rate, T(0)};            // :95
+    const V3<T> f_dot = (c.mass * inv_fn) * mul(R, hadamard(Kp, ev));   // :96
+    const V3<T> b3d_dot = reject(f_dot, b3d);                           // :97
+    const V3<T> inner = inv_n1 * (cross(b1c_dot, b3d) + cross(b1c, b3d_dot));       // |b1c x b3d| = |b3d x b1c|
+    const V3<T> b2d_dot = reject(inner, b2d);                           // :98-99
+    const V3<T> b1d_dot = cross(b3d_dot, b2d) + cross(b3d, b2d_dot);    // :100
+    // W = R_des @ R_dot_des (no-op transpose, :102); w_des = (W21, W02, W10) (:103)
+    w_des = {m_fma(b1d.z, b2d_dot.x, m_fma(b2d.z, b2d_dot.y, b3d.z * b2d_dot.z)),
+             m_fma(b1d.x, b3d_dot.x, m_fma(b2d.x, b3d_dot.y, b3d.x * b3d_dot.z)),
+             m_fma(b1d.y, b1d_dot.x, m_fma(b2d.y, b1d_dot.y, b3d.y * b1d_dot.z))};
+  }
   if (aux) {
     aux->force = fbz;                                                   // f_w^T (R e3)  (:107)
     aux->w_des = w_des;
@@ -895,11 +951,12 @@ MDS_HD void geometric_control(const Consts<T>& c, V3<T> p_rel, const M3<T>& R, V
   }
   // e_R = 1/2 KR vee(R_des^T R - R^T R_des), vee(M) = (-M12, M02, -M01)  (:109, :36-44)
   const V3<T> r0 = col(R, 0), r1 = col(R, 1), r2 = col(R, 2);
-  const T E12 = dot(b2d, r2) - dot(b3d, r1);
+  // (Y0: b2d.x = 0 -- the dots with b2d and the first row of R_des w_des lose that term)
+  const T E12 = (Y0 ? m_fma(b2d.y, r2.y, b2d.z * r2.z) : dot(b2d, r2)) - dot(b3d, r1);
   const T E02 = dot(b1d, r2) - dot(b3d, r0);
-  const T E01 = dot(b1d, r1) - dot(b2d, r0);
+  const T E01 = dot(b1d, r1) - (Y0 ? m_fma(b2d.y, r0.y, b2d.z * r0.z) : dot(b2d, r0));
   const V3<T> eR = {c.kR_half[0] * E12, c.kR_half[1] * E02, c.kR_half[2] * E01};        // (-1/2 kR0, 1/2 kR1, -1/2 kR2)
-  const V3<T> Rdw = {m_fma(b1d.x, w_des.x, m_fma(b2d.x, w_des.y, b3d.x * w_des.z)),
+  const V3<T> Rdw = {Y0 ? m_fma(b1d.x, w_des.x, b3d.x * w_des.z) : m_fma(b1d.x, w_des.x, m_fma(b2d.x, w_des.y, b3d.x * w_des.z)),
                      m_fma(b1d.y, w_des.x, m_fma(b2d.y, w_des.y, b3d.y * w_des.z)),
                      m_fma(b1d.z, w_des.x, m_fma(b2d.z, w_des.y, b3d.z * w_des.z))};
   const V3<T> ew = w - mulT(R, Rdw);

@@ -410,6 +410,17 @@ class BaseAviary:
         self._require_open()
         capi.check(self._lib.mds_set_rollout_form(self._h, C.c_int(int(form)), C.c_int(int(steps_per_launch))), "mds_set_rollout_form")
 
+    def traj_yaw_free(self) -> bool:
+        """True when every Lemniscate of the last ``set_trajectories`` has ``yaw_rate == 0`` (mds_traj_yaw_free): the fused geometric step and
+        rollout then run the yaw-free kernels (results ``==`` the general ones'; only the sign of an exact zero may differ)."""
+        self._require_open()
+        return bool(self._lib.mds_traj_yaw_free(self._h))
+
+    def set_traj_specialisation(self, on: bool = True):
+        """``False`` keeps this env on the general kernels whatever its trajectories (mds_set_traj_specialisation; default on)."""
+        self._require_open()
+        capi.check(self._lib.mds_set_traj_specialisation(self._h, C.c_int(1 if on else 0)), "mds_set_traj_specialisation")
+
     def rollout_form_for(self, n_steps: int) -> int:
         self._require_open()
         return int(self._lib.mds_rollout_form_for(self._h, C.c_int(int(n_steps))))

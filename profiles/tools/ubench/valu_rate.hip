@@ -1,7 +1,9 @@
 // VALU issue-rate microbenchmark for gfx950: cycles per wave64 instruction for scalar and packed fp32, dependent and independent chains,
 // and for the instruction classes the rollout step loop spends its slots on besides v_fma_f32 (compare-and-select pairs with their
 // hazard s_nop, v_med3_f32, v_max_f32 with an SGPR operand, v_mov_b32 from an SGPR, s_nop 1, v_rsq_f32, v_fma_f64, and the bookkeeping
-// classes: v_mul_lo_u32, v_cvt_f64_f32, v_add_f64, v_readfirstlane_b32, v_lshl_add_u64), at 1..8 waves per SIMD.  Build: hipcc --offload-arch=gfx950 -O3 -o valu_rate valu_rate.hip ; run: ./valu_rate
+// classes: v_mul_lo_u32, v_cvt_f64_f32, v_add_f64, v_readfirstlane_b32, v_lshl_add_u64), at 1..8 waves per SIMD.  Build with the library's flags
+// (__graft_entry__.HIPCC_FLAGS; without -fno-slp-vectorize the SLP vectoriser packs the "scalar fma, 8 independent" mode into v_pk_fma_f32 and
+// the figure is a packed one): hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -Wno-pass-failed -o valu_rate valu_rate.hip ; run: ./valu_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
