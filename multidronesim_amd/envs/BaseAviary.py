@@ -25,6 +25,23 @@ _PHYSICS_MAP = {Physics.DYN: capi.MDS_PHYSICS_DYN, Physics.PYB: capi.MDS_PHYSICS
                 Physics.PYB_DW: capi.MDS_PHYSICS_DYN_DW, Physics.PYB_GND_DRAG_DW: capi.MDS_PHYSICS_DYN_GND_DRAG_DW}
 _MODEL_MAP = {DroneModel.CF2X: capi.MDS_CF2X, DroneModel.CF2P: capi.MDS_CF2P}
 _PYB_SUBSTITUTED = (Physics.PYB, Physics.PYB_DRAG, Physics.PYB_GND, Physics.PYB_DW, Physics.PYB_GND_DRAG_DW)
+_CONSTANT_KEYS = {"M": 1, "L": 1, "KF": 1, "KM": 1, "J": 3, "G": 1, "thrust2weight": 1, "drag_coeff": 3}   # MdsConfig field -> length
+
+
+def apply_constants(cfg, constants):
+    """Overwrite the urdf constants of an ``MdsConfig`` (mds_default_config's, which include/mds.h documents as caller-settable) with the
+    entries of ``constants``: M, L, KF, KM, G, thrust2weight (scalars), J, drag_coeff (3 values each).  Any other key is a ValueError."""
+    for key, val in (constants or {}).items():
+        if key not in _CONSTANT_KEYS:
+            raise ValueError(f"constants: unknown key {key!r} (allowed: {', '.join(_CONSTANT_KEYS)})")
+        if _CONSTANT_KEYS[key] == 1:
+            setattr(cfg, key, float(val))
+        else:
+            v = np.asarray(val, dtype=np.float64).reshape(-1)
+            if v.shape != (3,):
+                raise ValueError(f"constants[{key!r}] needs 3 values, got {v.size}")
+            setattr(cfg, key, (C.c_double * 3)(*v))
+    return cfg
 
 
 class BaseAviary:
@@ -34,6 +51,9 @@ class BaseAviary:
     -> obs[D,20]``.  With a torch tensor in (any ``num_envs``) everything stays on the GPU:
     ``step(action[E,D,4]) -> obs[E,D,20]``.  obs layout ([UPSTREAM] _getDroneStateVector):
     pos3 | quat4 xyzw | rpy3 | vel3 | ang_v3 (world) | last clipped RPM4.
+
+    ``constants`` (keyword only) replaces urdf constants of the built-in model before the handle is created: a dict with any of
+    ``M, L, KF, KM, J`` (3 values), ``G, thrust2weight, drag_coeff`` (3 values).
 
     ``Physics.PYB`` (the reference's default, PIDEnv.py:19) is served by the explicit
     ``Physics.DYN`` rigid-body model -- there is no Bullet here; ``PYB_DRAG`` adds upstream's
@@ -48,7 +68,7 @@ class BaseAviary:
                  initial_xyzs=None, initial_rpys=None, physics: Physics = Physics.PYB, pyb_freq: int = 240,
                  ctrl_freq: int = 240, gui=False, record=False, obstacles=False, user_debug_gui=True,
                  output_folder="results", *, num_envs: int = 1, dtype="float32", integrator: str = "euler",
-                 device: int | None = None, track_last_rpm: bool | None = None):
+                 device: int | None = None, track_last_rpm: bool | None = None, constants: dict | None = None):
         lib = capi.load_library()
         if isinstance(drone_model, str):
             drone_model = DroneModel(drone_model)
@@ -95,6 +115,7 @@ class BaseAviary:
         # _computeObs()[..., 16:20] after a step: kept by the library when the env is used the reference's way (one env);
         # batched envs read the last clipped RPM from the obs step() returns and skip the extra 16 B per drone-step
         cfg.track_last_rpm = int(self.NUM_ENVS == 1 if track_last_rpm is None else track_last_rpm)
+        apply_constants(cfg, constants)      # the caller's own drone: every kernel's constant block and the mirrors below see it
         self._cfg = cfg
         # urdf constants ([UPSTREAM] _parseURDFParameters) + derived attributes the reference reads off env
         self.M, self.L, self.KF, self.KM = cfg.M, cfg.L, cfg.KF, cfg.KM

@@ -40,7 +40,18 @@ GAINS = {
                    D_TOR=0.5 * np.array([20000., 20000., 12000.])),
     # keeps the torque inside +-3200 at large attitude errors, so the attitude integral shows in the output
     "probe": dict(_HALF, P_TOR=np.array([300., 300., 300.]), I_TOR=np.array([1500., 1500., 500.]), D_TOR=np.array([50., 50., 50.])),
+    # three distinct, non-zero entries in every vector, each within +-40 % of "halved" (its two zero I_TOR entries: around 250): in the other
+    # two sets the x entry equals the y entry everywhere, so a kernel that swapped them computes the same numbers
+    "skew": dict(P_FOR=np.array([.16, .26, .55]), I_FOR=np.array([.02, .032, .027]), D_FOR=np.array([.08, .13, .22]),
+                 P_TOR=np.array([28000., 44000., 34000.]), I_TOR=np.array([250., 325., 190.]), D_TOR=np.array([8000., 13000., 7000.])),
 }
+
+
+def mirrored(gains):
+    """A gain set with the x and y entries of all six vectors swapped."""
+    return {k: np.array([v[1], v[0], v[2]]) for k, v in gains.items()}
+
+
 CLAMPS = ("xy2", "z015", "rp1", "tq3200", "min_pwm", "max_pwm")
 
 

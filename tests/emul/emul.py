@@ -38,9 +38,22 @@ def dp(a):
     return a.ctypes.data_as(_PD)
 
 
+def set_structs(cfg, gstruct, constants=None, gains=None):
+    """Write a ``constants=`` dict into an MdsConfig and an oracle-style gains dict (Kp, Kv, KR, Kw, g, max_tilt) into an MdsGeometricGains."""
+    from multidronesim_amd.envs.BaseAviary import apply_constants
+    apply_constants(cfg, constants)
+    for k, v in (gains or {}).items():
+        if k in ("Kp", "Kv", "KR", "Kw"):
+            setattr(gstruct, k, (C.c_double * 3)(*np.broadcast_to(np.asarray(v, dtype=np.float64), (3,))))
+        else:
+            setattr(gstruct, {"max_tilt": "max_tilt_angle"}.get(k, k), float(v))
+
+
 class Emul:
     def __init__(self, dtype="f32", num_envs=1, num_drones=1, pyb_freq=100, ctrl_freq=100, physics=0, integrator=0,
-                 model=MDS_CF2P):
+                 model=MDS_CF2P, constants=None, gains=None):
+        """``constants``: a CtrlAviary(constants=...) dict written into the config; ``gains``: Kp / Kv / KR / Kw (3 values each), g, max_tilt
+        written into the geometric gains -- both before the handle is created."""
         L = lib()
         comp = dtype.startswith("f32c")  # fp32 arithmetic, compensated accumulation: "f32c" = MDS_F32C as the device stores it (residuals
         mask = {"f32c": 8, "f32c13": 15}.get(dtype, 8) if comp else 0      # of the body rates only); "f32c13" = all 13, "f32c:<mask>" = study
@@ -55,6 +68,7 @@ class Emul:
         self.cfg.pyb_freq, self.cfg.ctrl_freq = pyb_freq, ctrl_freq
         self.cfg.physics, self.cfg.integrator = physics, integrator
         self.n = num_envs * num_drones
+        set_structs(self.cfg, self.gains, constants, gains)
         self.h = C.c_void_p(getattr(L, f"emul_create_{dtype}")(C.byref(self.cfg), C.byref(self.gains)))
         if comp:
             self._f("emul_set_comp")(self.h, C.c_int(1))

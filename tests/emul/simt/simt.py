@@ -59,13 +59,15 @@ def build_tsan(force=False):
     return EXE_TSAN
 
 
-def _structs(D, E, cbf_fields, pyb_freq=100, ctrl_freq=100):
+def _structs(D, E, cbf_fields, pyb_freq=100, ctrl_freq=100, constants=None, gains=None):
     from multidronesim_amd import _capi as capi
     lib = capi.load_library()
-    cfg, gains, p = capi.MdsConfig(), capi.MdsGeometricGains(), capi.MdsCbfParams()
+    cfg, gains_struct, p = capi.MdsConfig(), capi.MdsGeometricGains(), capi.MdsCbfParams()
     capi.check(lib.mds_default_config(capi.MDS_CF2P, C.byref(cfg)), "mds_default_config")
-    capi.check(lib.mds_default_geometric_gains(C.byref(gains)), "mds_default_geometric_gains")
+    capi.check(lib.mds_default_geometric_gains(C.byref(gains_struct)), "mds_default_geometric_gains")
     cfg.num_envs, cfg.num_drones, cfg.pyb_freq, cfg.ctrl_freq, cfg.dtype = E, D, pyb_freq, ctrl_freq, capi.MDS_F64
+    from tests.emul.emul import set_structs
+    set_structs(cfg, gains_struct, constants, gains)       # a CtrlAviary(constants=...) dict, oracle-style geometric gains
     for k, v in cbf_fields.items():
         if isinstance(v, (list, tuple, np.ndarray)):
             arr = getattr(p, k)
@@ -73,16 +75,16 @@ def _structs(D, E, cbf_fields, pyb_freq=100, ctrl_freq=100):
                 arr[j] = float(x)
         else:
             setattr(p, k, v)
-    return cfg, gains, p
+    return cfg, gains_struct, p
 
 
 DTYPE_CODE = {"float32": 0, "float64": 1, "float16": 2, "float32c": 3}
 
 
-def run(mode, dtype, E, D, n_steps, cbf_fields, obstacles, arrays, timeout=900, tsan=False, nominal=0):
+def run(mode, dtype, E, D, n_steps, cbf_fields, obstacles, arrays, timeout=900, tsan=False, nominal=0, constants=None, gains=None):
     """-> the bytes of out.bin.  obstacles: [n_obs, 4] (xyz, r).  arrays: the mode's float64 arrays, concatenated in order."""
     exe = build_tsan() if tsan else build()[2 if mode == 3 else mode]
-    cfg, gains, p = _structs(D, E, cbf_fields)
+    cfg, gains, p = _structs(D, E, cbf_fields, constants=constants, gains=gains)
     ob = np.zeros(64)
     ob[:np.asarray(obstacles).size] = np.asarray(obstacles, dtype=np.float64).reshape(-1)
     with tempfile.TemporaryDirectory() as td:
@@ -133,13 +135,13 @@ def rollout_o3(dtype, t0, K, P, state13, rpm_echo, steps, cbf_fields, obstacles,
     return obs, slog, it, err
 
 
-def headline(dtype, form, t0, P, state13, steps, actions=None, tsan=False):
+def headline(dtype, form, t0, P, state13, steps, actions=None, tsan=False, constants=None, gains=None):
     """Mode 4: form 0 k_step_geometric per step, 1 k_rollout_geometric (log ring), 2 k_step on an action table [3, E, D, 4], 3 k_rollout_step,
     4 k_rollout_geometric rewriting one [n, 20] array every step.
     -> (obs [E,D,20], state13 [E,D,13] world, action_out [E,D,4] (form 0), stderr)"""
     E, D = P.shape[0], P.shape[1]
     arrays = [np.array([t0]), P, state13] + ([actions] if form in (2, 3) else [])
-    raw, err = run(4, dtype, E, D, steps, {"order": 2}, np.zeros((0, 4)), arrays, tsan=tsan, nominal=form)
+    raw, err = run(4, dtype, E, D, steps, {"order": 2}, np.zeros((0, 4)), arrays, tsan=tsan, nominal=form, constants=constants, gains=gains)
     n = E * D
     obs = np.frombuffer(raw[:n * 160], dtype=np.float64).reshape(E, D, 20)
     st = np.frombuffer(raw[n * 160:n * 264], dtype=np.float64).reshape(E, D, 13)

@@ -219,7 +219,7 @@ class FedCE:
         self.D = len(init_xyzs)
         self.init_xyzs, self.init_rpys = np.asarray(init_xyzs, float), np.asarray(init_rpys, float)
         self.target_pos, self.target_rpys = np.asarray(target_pos, float), np.asarray(target_rpys, float)
-        self.env = O.AviaryOracle(self.init_xyzs, self.init_rpys, pyb_freq=freq, ctrl_freq=freq, physics=physics)
+        self.env = O.AviaryOracle(self.init_xyzs, self.init_rpys, c, pyb_freq=freq, ctrl_freq=freq, physics=physics)
         self.wind = np.array([wind, 0.0, 0.0])
         self.dlqr = DLQR(self.D, c)
         self.obs_log = []

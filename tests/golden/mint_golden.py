@@ -264,6 +264,98 @@ def mint_dyn_wrench_accel(ref):
     print("dyn_wrench_accel", u.shape, "clipped rows:", int(((rpm < 0) | (rpm > env.MAX_RPM)).any(axis=1).sum()))
 
 
+def aniso_set():
+    """The x/y-asymmetric parameter set of tests/aniso_cases.py (constants A, gains A): defined there, once."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from tests import aniso_cases as AC
+    return AC
+
+
+def make_env_aniso():
+    """make_env() with M, L, KF, KM, J of constants A (G and the thrust-to-weight ratio stay stock)."""
+    cs = aniso_set().CONSTANTS
+    env = make_env()
+    env.M, env.L, env.KF, env.KM = cs["M"], cs["L"], cs["KF"], cs["KM"]
+    env.J = np.diag(cs["J"])
+    env.MAX_RPM = np.sqrt(2.25 * env.M * env.G / (4 * env.KF))
+    env.MAX_THRUST = 4 * env.KF * env.MAX_RPM ** 2
+    return env
+
+
+def mint_geometric_aniso(ref):
+    """mint_geometric's three case families (96 + 16 + 16 rows) through the reference's GeometricControl on an env with constants A and with
+    Kp / Kv / KR / Kw overwritten with gains A after construction: three distinct entries in J and in every gain vector, so that
+    (Jy - Jx) wx wy and every x/y index of the controller show in the output."""
+    AC = aniso_set()
+    env = make_env_aniso()
+    Lem = ref["lem"].Lemniscate
+    G = ref["geo"].GeometricControl
+    rng = np.random.default_rng(40)
+    n_rand, n_tilt, n_clip = 96, 16, 16
+    obs_list, des_list = [], []
+    traj = Lem(center=np.array([0, 0, .5]), omega=1.5, yaw_rate=0.3)
+    for k in range(n_rand + n_tilt + n_clip):
+        t = rng.uniform(0.5, 20)
+        if k < n_rand:          # yaw = pi sin(0.3 t): within 0.25 .. 1.05 s of a zero crossing the desired yaw is non-zero and below 1 rad (no yaw-torque clip)
+            t = abs((np.pi / 0.3) * rng.integers(0, 3) + rng.choice([-1.0, 1.0]) * rng.uniform(0.25, 1.05))
+        pos, vel, acc, yaw, om = traj(t)
+        if k < n_rand:                                                 # (a) random states near the trajectory: attitudes +-0.4, position noise 0.15 m
+            o = random_obs(rng, 1, pos, vel, euler_max=0.4, w_max=1.0, pos_noise=0.15, vel_noise=0.2)[0]
+            o[9] += yaw                                                # attitude within 0.4 rad of the desired one, yaw included
+            o[3:7] = Rotation.from_euler("xyz", o[7:10]).as_quat()
+        elif k < n_rand + n_tilt:                                      # (b) tilt clamp: large lateral position error
+            o = random_obs(rng, 1, pos + np.array([rng.uniform(3, 8) * rng.choice([-1, 1]), rng.uniform(-6, 6), 0.0]), vel)[0]
+        else:                                                          # (c) min-thrust clip: far above the target, moving up fast, flipped attitude
+            o = random_obs(rng, 1, pos + np.array([0.0, 0.0, rng.uniform(4, 12)]), vel + np.array([0, 0, 3.0]), euler_max=1.4, w_max=6.0)[0]
+        obs_list.append(o)
+        des_list.append(np.hstack([pos, vel, acc, yaw, om]))
+    obs, des = np.array(obs_list), np.array(des_list)
+    n = obs.shape[0]
+    rpm, force, w_des, R_des = np.zeros((n, 4)), np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3, 3))
+    for i in range(n):
+        ctrl = G(env)
+        ctrl.Kp, ctrl.Kv, ctrl.KR, ctrl.Kw = (np.array(AC.GAINS[k], dtype=np.float64) for k in ("Kp", "Kv", "KR", "Kw"))
+        ctrl.set_desired_trajectory(0, des[i, 0:3].copy(), des[i, 3:6].copy(), des[i, 6:9].copy(), des[i, 9], des[i, 10])
+        rpm[i] = ctrl.compute(obs[i].copy())
+        force[i], w_des[i], R_des[i] = ctrl.compute(obs[i].copy(), return_omegas=True)
+    np.savez_compressed(OUT + "/geometric_compute_aniso.npz", obs=obs, des=des, rpm=rpm, force=force, w_des=w_des, R_des=R_des,
+                        n_rand=n_rand, n_tilt=n_tilt, n_clip=n_clip, M=env.M, L=env.L, KF=env.KF, KM=env.KM, J=np.diag(env.J),
+                        **{k: np.array(AC.GAINS[k]) for k in ("Kp", "Kv", "KR", "Kw")}, **META)
+    lo = 9440.3
+    print("geometric_aniso", n, "minclip rows:", int((np.abs(rpm - lo) < 1e-6).any(axis=1).sum()), "of them in family (a):",
+          int((np.abs(rpm[:n_rand] - lo) < 1e-6).any(axis=1).sum()), "maxclip rows:", int((rpm > env.MAX_RPM - 1e-6).any(axis=1).sum()))
+
+
+def mint_dyn_wrench_accel_aniso(ref):
+    """mint_dyn_wrench_accel with constants A: action_to_input on an env with A's KF, KM, L and QuadrotorDynamics.dynamics with m, g and
+    Jxx != Jyy != Jzz from A, 192 rows (near hover, wide, beyond MAX_RPM): w_dot carries (Jy - Jx) wx wy / Jz, which is zero with the urdf's J."""
+    env = make_env_aniso()
+    mc = ref["mc"]
+    q = ref["dyn"].QuadrotorDynamics(sim_freq=240)
+    q.m, q.g = env.M, env.G
+    q.Jxx, q.Jyy, q.Jzz = env.J[0, 0], env.J[1, 1], env.J[2, 2]
+    q.J = np.diag([q.Jxx, q.Jyy, q.Jzz])
+    q.J_inv = np.linalg.inv(q.J)
+    rng = np.random.default_rng(41)
+    n = 192
+    hover = np.sqrt(env.M * env.G / (4 * env.KF))
+    rpm = np.empty((n, 4))
+    rpm[:64] = hover * (1 + 0.03 * rng.normal(size=(64, 4)))
+    rpm[64:128] = rng.uniform(0, env.MAX_RPM, size=(64, 4))
+    rpm[128:] = rng.uniform(-0.1 * env.MAX_RPM, 1.3 * env.MAX_RPM, size=(64, 4))        # clipped on both sides
+    quat = Rotation.from_euler("xyz", rng.uniform(-1.2, 1.2, size=(n, 3))).as_quat()
+    R = Rotation.from_quat(quat).as_matrix()
+    pos = rng.normal(size=(n, 3))
+    vel = rng.normal(size=(n, 3)) * 2
+    rates = rng.normal(size=(n, 3)) * 3
+    u = np.array([mc.action_to_input(env, a.copy()) for a in rpm])
+    state = np.hstack([pos, R.reshape(n, 9), vel, rates])
+    ydot = np.array([q.dynamics(0.0, s, ui) for s, ui in zip(state, u)])
+    np.savez_compressed(OUT + "/dyn_wrench_accel_aniso.npz", rpm=rpm, quat=quat, pos=pos, vel=vel, rates=rates, u=u, v_dot=ydot[:, 6:9],
+                        w_dot=ydot[:, 9:12], max_rpm=env.MAX_RPM, m=env.M, g=env.G, J=np.diag(env.J), L=env.L, KF=env.KF, KM=env.KM, **META)
+    print("dyn_wrench_accel_aniso", u.shape, "clipped rows:", int(((rpm < 0) | (rpm > env.MAX_RPM)).any(axis=1).sum()))
+
+
 def mint_attitude_flow(ref):
     """The attitude kinematics the reference tree states: body-frame angular velocity, R_dot = R hat(w)
     (model/dynamics.py:62-66 hat_map, :102 R_dot).  For a constant body rate its flow over dt is R(dt) = R expm(hat(w) dt): the
@@ -731,6 +823,8 @@ if __name__ == "__main__":
     mint_mixer(ref)
     mint_dynamics(ref)
     mint_dyn_wrench_accel(ref)
+    mint_geometric_aniso(ref)
+    mint_dyn_wrench_accel_aniso(ref)
     mint_attitude_flow(ref)
     mint_euler_convention(ref)
     mint_closed_loop_reference_in_the_loop(ref)

@@ -27,8 +27,8 @@ def c2_setup(E, D, seed=0, offset=5.0, phase="c2", omega=1.5, z0=0.5, yaw_rate=0
 
 
 def oracle_closed_loop(xyz, rpy, P, steps, pyb_freq=100, ctrl_freq=100, physics="dyn", integrator="euler",
-                       consts=O.CF2P, record_every=None):
-    """Reference loop shape (simulations/EnvGeometric.py:431-473) on the oracle."""
+                       consts=O.CF2P, record_every=None, gains=None):
+    """Reference loop shape (simulations/EnvGeometric.py:431-473) on the oracle.  ``gains``: passed to O.geometric_compute."""
     n = xyz.reshape(-1, 3).shape[0]
     Pf = P.reshape(-1, 7)
     ora = O.AviaryOracle(xyz.reshape(-1, 3), rpy.reshape(-1, 3), consts, pyb_freq, ctrl_freq, physics, integrator)
@@ -37,7 +37,7 @@ def oracle_closed_loop(xyz, rpy, P, steps, pyb_freq=100, ctrl_freq=100, physics=
     out = [obs]
     for k in range(steps):
         pos, vel, acc, yaw, yd = O.lemniscate(t, Pf[:, 0], Pf[:, 1], Pf[:, 2:5], Pf[:, 5], Pf[:, 6])
-        rpm = O.geometric_compute(obs, pos, vel, acc, yaw, yd, consts)
+        rpm = O.geometric_compute(obs, pos, vel, acc, yaw, yd, consts, gains=gains)
         obs = ora.step(rpm)
         t += ora.CTRL_TIMESTEP
         if record_every and (k + 1) % record_every == 0:
@@ -72,12 +72,14 @@ def open_loop_setup(n, seed=1, tilt=0.02):
 
 
 def oracle_cbf_closed_loop(xyz, rpy, P, steps, Kcbf, umax, safety_radius, zscale, x_obs, obs_r, pyb_freq=100, ctrl_freq=100,
-                           consts=O.CF2P, nominal="geometric", order=2, Fmin=None, Fmax=None, first_rpm=0.0, physics="dyn", record_at=None):
+                           consts=O.CF2P, nominal="geometric", order=2, Fmin=None, Fmax=None, first_rpm=0.0, physics="dyn", record_at=None,
+                           gains=None, filter_log=None):
     """simulations/CBFTest.py:303-350 on the oracle, per env: geometric nominal (return_omegas) ->
     u_hat = (force - M G, w_des), xdes = [0,0,yaw, vel, pos] -> ECBF QP (fallback to nominal) ->
     + M G -> ThrustOmega low level -> env.step.  order 3 / nominal "lqr_yank_omega": the loop of
     simulations/CBFTestOrd3.py:306-352 (yank - M G, xdes with G M in slot 3, YankOmega low level, nothing added back).
-    Returns (obs [E,D,20], status history [steps,E]); with record_at = (m1, m2, ...) also {m: obs after m steps}."""
+    Returns (obs [E,D,20], status history [steps,E]); with record_at = (m1, m2, ...) also {m: obs after m steps}.
+    ``gains``: passed to O.geometric_compute; ``filter_log``: a list that receives, per step, max |u_safe - u_nominal| per env [E]."""
     E, D = xyz.shape[0], xyz.shape[1]
     n = E * D
     Pf = P.reshape(-1, 7)
@@ -99,7 +101,7 @@ def oracle_cbf_closed_loop(xyz, rpy, P, steps, Kcbf, umax, safety_radius, zscale
             unom = O.lqr_yank_omega_compute(obs, pos, vel, yaw, Kyo, consts)
             unom[:, 0] -= consts.M * consts.G
         else:
-            force, w_des, _ = O.geometric_compute(obs, pos, vel, acc, yaw, yd, consts, return_omegas=True)
+            force, w_des, _ = O.geometric_compute(obs, pos, vel, acc, yaw, yd, consts, gains=gains, return_omegas=True)
             unom = np.concatenate([(force - consts.M * consts.G)[:, None], w_des], axis=1)
         if order == 3:
             xdes = np.concatenate([np.zeros((n, 2)), yaw[:, None], np.full((n, 1), consts.G * consts.M), vel, pos], axis=1)
@@ -115,6 +117,8 @@ def oracle_cbf_closed_loop(xyz, rpy, P, steps, Kcbf, umax, safety_radius, zscale
             usafe[sl], st[e] = O.cbf_filter(x[sl], xdes[sl], unom[sl], order, Kcbf, umax, safety_radius, zscale, consts,
                                             np.array(x_obs) if x_obs is not None else None, obs_r, **kw)
         hist.append(st)
+        if filter_log is not None:
+            filter_log.append(np.abs(usafe - unom).reshape(E, -1).max(axis=1))
         if order == 2:
             usafe[:, 0] += consts.M * consts.G
         rpm = ll.compute_low_level(usafe, obs, ora.CTRL_TIMESTEP)

@@ -57,6 +57,43 @@ def test_default_config_matches_urdf_constants(lib):
     assert g.g == 9.81 and g.max_tilt_angle == pytest.approx(40 * np.pi / 180)
 
 
+def test_constants_dict_is_validated_and_written_into_the_config(lib):
+    """CtrlAviary(constants=...) -- the env constructor needs a device, so the dict -> MdsConfig step is tested as the plain function it is:
+    every allowed key lands in its field, nothing else moves, an unknown key or a 3-vector of the wrong length is a ValueError, and the
+    result still passes mds_create's validation (it fails on the missing device, or succeeds, not on the config)."""
+    import inspect
+    from multidronesim_amd.envs.BaseAviary import BaseAviary, apply_constants
+    from multidronesim_amd.envs.CtrlAviary import CtrlAviary
+    cfg, ref = capi.MdsConfig(), capi.MdsConfig()
+    for c in (cfg, ref):
+        assert lib.mds_default_config(capi.MDS_CF2P, C.byref(c)) == 0
+    assert apply_constants(cfg, None) is cfg and bytes(cfg) == bytes(ref)                 # absent: nothing changes
+    apply_constants(cfg, {})
+    assert bytes(cfg) == bytes(ref)
+    full = dict(M=0.031, L=0.0432, KF=2.9e-10, KM=8.6e-12, J=(2.1e-5, 2.9e-5, 3.6e-5), G=9.81, thrust2weight=2.0, drag_coeff=np.array([7.5e-7, 11.5e-7, 9.0e-7]))
+    apply_constants(cfg, full)
+    assert (cfg.M, cfg.L, cfg.KF, cfg.KM, cfg.G, cfg.thrust2weight) == (0.031, 0.0432, 2.9e-10, 8.6e-12, 9.81, 2.0)
+    assert list(cfg.J) == [2.1e-5, 2.9e-5, 3.6e-5] and list(cfg.drag_coeff) == [7.5e-7, 11.5e-7, 9.0e-7]
+    assert (cfg.num_envs, cfg.num_drones, cfg.dtype, cfg.physics, cfg.drone_model) == (ref.num_envs, ref.num_drones, ref.dtype, ref.physics, ref.drone_model)
+    apply_constants(cfg, {"J": (1e-5, 2e-5, 3e-5)})                                       # one key: the others stay
+    assert list(cfg.J) == [1e-5, 2e-5, 3e-5] and cfg.M == 0.031
+    for bad in ({"Jx": 1.0}, {"m": 0.03}, {"num_envs": 4}, {"J_INV": (1, 1, 1)}, {"J": (1e-5, 2e-5)}, {"drag_coeff": 1e-6}):
+        with pytest.raises(ValueError):
+            apply_constants(cfg, bad)
+    h = C.c_void_p()
+    cfg.num_envs = cfg.num_drones = 1
+    rc = lib.mds_create(C.byref(cfg), C.byref(h))
+    import torch
+    if torch.cuda.is_available():
+        assert rc == 0
+        lib.mds_destroy(h)
+    else:
+        assert rc in (-3, -2) and not h.value          # HIP error: no device -- not MDS_EINVAL
+    p = inspect.signature(BaseAviary.__init__).parameters["constants"]
+    assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is None                 # keyword only; CtrlAviary passes it through **batch_kwargs
+    assert "batch_kwargs" in inspect.signature(CtrlAviary.__init__).parameters
+
+
 def test_struct_layout_matches_header(lib):
     # 10 int32 + (4 + 3 + 2 + 3) doubles ; 12 + 2 doubles
     assert C.sizeof(capi.MdsConfig) == 10 * 4 + 12 * 8

@@ -1,6 +1,6 @@
 """dslpid_control (csrc/mds_math.hpp) on the CPU: the g++ build of the shipped header (tests/emul/dslpid_emul.cpp) against the float64
 oracle (oracle/np_oracle.py, DSLPIDOracle), open loop, call by call, on the case set of tests/dslpid_cases.py -- 333 drones x 24 calls,
-CF2P and CF2X mixers, 240 Hz and 10 Hz, PIDEnv's halved gains and the probe gains, float64 and float32 -- and the properties of
+CF2P and CF2X mixers, 240 Hz and 10 Hz, PIDEnv's halved gains, the probe gains and the x/y-asymmetric skew gains, float64 and float32 -- and the properties of
 that case set itself, asserted on the oracle alone: every clamp reached from both sides, most outputs unsaturated, no
 ill-conditioned case, and each clamp's removal visible far above the gate.
 
@@ -12,8 +12,13 @@ why 240 Hz with the halved defaults stands out):
     configuration           S          float32 gate   float32 shim error   float64 shim error
     240 Hz, halved gains    7.07e-06   2.88e-05       1.15e-05             2.6e-14
     10 Hz,  halved gains    2.97e-07   1.66e-06       7.57e-07             2.4e-15
-    240 Hz, probe gains     6.48e-08   7.36e-07       2.90e-07             6.7e-16
+    240 Hz, probe gains     6.03e-08   7.18e-07       2.90e-07             6.7e-16
     10 Hz,  probe gains     5.50e-09   4.99e-07       2.61e-07             6.7e-16
+    240 Hz, skew gains      7.47e-06   3.04e-05       1.35e-05             2.9e-14
+    10 Hz,  skew gains      3.21e-07   1.76e-06       7.13e-07             2.4e-15
+
+("skew": three distinct entries in each of the six gain vectors -- in the other two sets the x entry equals the y entry everywhere.  The draws
+are conditioned on all three sets, which redrew six drones of the 240 Hz set and two of the 10 Hz set when "skew" joined.)
 
 The float32 reference runs with the handle's dt, float32(1 / ctrl_freq).  CPU only."""
 import ctypes as C

@@ -11,8 +11,10 @@ and dt.  Measured on an MI355X (largest relative RPM error over both mixers):
     configuration           S          float32 gate   float32 device error   float64 device error
     240 Hz, halved gains    7.07e-06   2.88e-05       1.18e-05              2.5e-14
     10 Hz,  halved gains    2.97e-07   1.66e-06       7.57e-07              2.4e-15
-    240 Hz, probe gains     6.48e-08   7.36e-07       2.85e-07              6.7e-16
+    240 Hz, probe gains     6.03e-08   7.18e-07       2.85e-07              6.7e-16
     10 Hz,  probe gains     5.50e-09   4.99e-07       2.61e-07              6.7e-16
+    240 Hz, skew gains      7.47e-06   3.04e-05       1.33e-05              2.9e-14
+    10 Hz,  skew gains      3.21e-07   1.76e-06       7.13e-07              2.4e-15
 """
 import types
 
