@@ -413,14 +413,16 @@ __device__ __forceinline__ void env_substep(const Consts<T>& c, const EnvFx<T>& 
   rotor_wrench(c, clipped, &thrust, &tau);
   if (fx.gnd) ground_effect(c, fx, s, s.p.z + org.z, clipped, &thrust, &tau);
   if (fx.dw) {
-    const V3<T> me = {s.p.x + org.x, s.p.y + org.y, s.p.z + org.z};
     const int e0 = (i / D) * D;
     T f = T(0);
     for (int j = e0; j < e0 + D; ++j) {
       if (j == i) continue;
       T a4[4];
       load4<S, T>(state_in + 4 * (size_t)j, a4);                                // (px, py, pz, qx) of env-mate j, before this substep
-      f += downwash_pair(fx, me, V3<T>{a4[0] + origin[j], a4[1] + origin[ld + j], a4[2] + origin[2 * ld + j]});
+      // the separation from local positions and origins differenced separately: world coordinates far from the world origin would
+      // round away the local frame's resolution (include/mds.h, mds_set_origin) before the difference is taken
+      f += downwash_pair(fx, V3<T>{(a4[0] - s.p.x) + (origin[j] - org.x), (a4[1] - s.p.y) + (origin[ld + j] - org.y),
+                                   (a4[2] - s.p.z) + (origin[2 * ld + j] - org.z)});
     }
     thrust += f;
   }

@@ -638,8 +638,9 @@ MDS_HD void ground_effect(const Consts<T>& c, const EnvFx<T>& fx, const State<T>
     tau->y += c.arm * (g[2] - g[0]);
   }
 }
-template <typename T> MDS_HD T downwash_pair(const EnvFx<T>& fx, V3<T> me, V3<T> other) {
-  const T dz = other.z - me.z, dx = other.x - me.x, dy = other.y - me.y;
+// d: the env-mate's position minus the drone's own
+template <typename T> MDS_HD T downwash_pair(const EnvFx<T>& fx, V3<T> d) {
+  const T dz = d.z, dx = d.x, dy = d.y;
   const T dxy = m_sqrt(m_fma(dx, dx, dy * dy));
   if (!(dz > T(0) && dxy < T(10))) return T(0);
   const T ratio = fx.prop_radius / (T(4) * dz), beta = m_fma(fx.dw2, dz, fx.dw3), u = dxy / beta;
