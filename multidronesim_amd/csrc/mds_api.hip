@@ -52,6 +52,10 @@ int fail(int code, const char* what) {
   snprintf(g_err, sizeof(g_err), "%s", what);
   return code;
 }
+int fail(int code, const char* who, const char* what) {          // "<entry point><what>": checks shared by several entry points
+  snprintf(g_err, sizeof(g_err), "%s%s", who, what);
+  return code;
+}
 
 #define MDS_HIP(call)                          \
   do {                                         \
@@ -211,7 +215,7 @@ constexpr size_t kSplitMinDrones = size_t(1) << 18;
 // 100 steps 17.4 -> 15.2, 2000 steps 17.4 -> 14.8 (profiles/r02_short_calls.log).
 constexpr int kSplitMinSteps = 16;
 // LDS bytes a half-shard workgroup occupies in a two-chain rollout: its launch carries unused dynamic LDS up to this
-// (launch_step_geometric says why)
+// (step_geometric says why)
 constexpr size_t kSplitLds = 32768;
 
 // The stream policy in one place (mds_set_rollout_streams; mds_rollout_streams_for reports it).  loop 0: the fused geometric /
@@ -274,11 +278,13 @@ static int split_streams_ready(mds_handle* h) {
   return MDS_OK;
 }
 
-// Entry / exit of a two-chain rollout.  Chain 0 is the caller's stream itself: its launches wait for nothing, and the call
-// costs two cross-stream dependencies in all (four, and 50 us per call, when both chains ran on internal streams).
+// Entry / exit of a two-chain rollout (step_loop below is their one caller).  Chain 0 is the caller's stream itself: its launches
+// wait for nothing, and the call costs two cross-stream dependencies in all (four, and 50 us per call, when both chains ran on
+// internal streams).
 // fork: the internal stream waits for everything enqueued on the caller's stream so far.
-// join: the caller's stream waits for chain 1 -- ALWAYS run once fork has been attempted, also when a launch in between
-// failed, so that the caller's stream keeps ordering whatever was enqueued (mds.h: the caller's stream orders the whole call).
+// join: the caller's stream waits for chain 1 -- step_loop runs it whenever it has attempted the fork, also when the fork itself or
+// a launch in between failed, so that the caller's stream keeps ordering whatever was enqueued (mds.h: the caller's stream orders
+// the whole call).
 static int split_fork(mds_handle* h, hipStream_t st) {
   MDS_HIP(hipEventRecord(h->split_ev[0], st));
   MDS_HIP(hipStreamWaitEvent(h->split_st, h->split_ev[0], 0));
@@ -291,6 +297,59 @@ static int split_join(mds_handle* h, hipStream_t st, int rc_body) {
   if (e != hipSuccess && rc == MDS_OK) rc = fail_hip(e, "two-chain rollout: join");
   return rc;
 }
+
+static int check_launches() {
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+
+// One step chain of a per-step rollout: its stream and the part [i0, i0 + n) of the shard it steps, in the caller's unit (256-drone
+// batches; envs in the CBF loop).  n == 0: the whole shard, launched as a single step call launches it.
+struct Chain {
+  hipStream_t st;
+  unsigned i0, n;
+};
+
+// envs [e0, e0 + ne) of the batch; slot selects the cost-class tables (0: whole batch, 1 / 2: halves of a two-stream rollout)
+struct EnvRange {
+  int e0, ne, slot;
+};
+
+// The driver of every one-launch-per-control-step rollout.  Control steps [k_first, n_steps) go through step(k, chains, n_chains),
+// called once per step: it enqueues the step on chain 0, then on chain 1, and advances whatever it carries from step to step (the
+// time, ring indices) once.  streams == 2 (rollout_streams_policy) with a shard that has a middle makes two chains: [0, mid) on the
+// caller's stream, [mid, total) on the internal one, forked before the first launch and always joined.  Only enqueues.
+template <typename Step>
+static int step_loop(mds_handle* h, hipStream_t st, int streams, unsigned mid, unsigned total, int k_first, int n_steps, Step& step) {
+  const bool two = streams == 2 && mid > 0;
+  const Chain chains[2] = {{st, 0, two ? mid : 0}, {h->split_st, mid, total - mid}};
+  h->last_rollout_streams = two ? 2 : 1;
+  int rc = two ? split_fork(h, st) : MDS_OK;
+  for (int k = k_first; k < n_steps && rc == MDS_OK; ++k) rc = step(k, chains, two ? 2 : 1);
+  if (rc == MDS_OK) rc = check_launches();
+  return two ? split_join(h, st, rc) : rc;
+}
+// the same for the loops over 256-drone batches: two chains when the policy says so and the shard has two batches
+template <typename Step> static int step_loop_batches(mds_handle* h, hipStream_t st, int k_first, int n_steps, Step& step) {
+  const unsigned nbatch = (unsigned)((h->n + kBlock - 1) / kBlock);
+  return step_loop(h, st, rollout_streams_policy(h, 0, n_steps), nbatch / 2, nbatch, k_first, n_steps, step);
+}
+
+// A rollout in launches of at most per_launch control steps: launch by launch, the step it starts at (k), its time -- advanced by
+// one += dt per step, as inside the kernels and in the reference loop, never k * dt -- and its slot of an n_slots-deep ring (0: no ring).
+//   for (Chunks c{...}; c.k < c.n_steps; c.advance(ks))  with ks = c.len(), or less where the caller cuts a launch short
+struct Chunks {
+  int n_steps, per_launch;
+  double t, dt;
+  int slot, n_slots;
+  int k = 0;
+  int len() const { return n_steps - k < per_launch ? n_steps - k : per_launch; }
+  void advance(int ks) {
+    for (int j = 0; j < ks; ++j) t += dt;
+    if (n_slots > 0) slot = (slot + ks) % n_slots;
+    k += ks;
+  }
+};
 
 // Run-time handle state -> template arguments.  Each helper calls a generic lambda with compile-time tags, so that a launch (its kernel
 // name and argument list) is written once, in ordinary code, inside the lambda.  They instantiate exactly the branches listed here.
@@ -370,12 +429,19 @@ extern "C" {
 
 // (C linkage like everything in this block; not part of include/mds.h)
 // helpers called across the two parts (defined once, in the part named)
-struct EnvRange;
+// what step_nominal_lowlevel does besides nominal controller -> low level -> env.step
+struct NominalStep {
+  bool with_filter = false;       // the ECBF QP between the nominal controller and the low level
+  EnvRange range = {0, -1, 0};    // the envs it steps (ne < 0: all of them)
+  bool have_nominal = false;      // the previous step's low-level launch has left this step's u_hat / xdes in the scratch (its want_next)
+  bool want_next = false;         // this step's low-level launch also computes the nominal input of the step at t_next (nominal 0 / 1 only)
+  double t_next = 0.0;
+};
 int step_env_plain(mds_handle* h, const void* action, void* obs, hipStream_t st, int first_substep, void* home = nullptr);              // part 1
 int step_env_ctrl(mds_handle* h, int ctrl, double t, const void* u_in, double thrust_offset, void* obs, void* act, hipStream_t st);     // part 1
 int rollout_fused(mds_handle* h, double t0, int n_steps, void* obs_log, void* obs_last, void* stream, int ctrl, const char* who);       // part 1
-int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, void* action, void* stream, bool with_filter,            // part 2
-                          const char* who, const EnvRange* rgp = nullptr, bool have_nominal = false, bool want_next = false, double t_next = 0.0);
+int step_lqr(mds_handle* h, double t, void* obs, void* act, hipStream_t st);                                                            // part 2
+int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, void* action, hipStream_t st, const NominalStep& o = {}); // part 2
 
 #if MDS_PART & 1
 int mds_version(void) { return MDS_VERSION; }
@@ -682,16 +748,20 @@ int mds_get_obs(mds_handle* h, void* obs, void* stream) {
   return MDS_OK;
 }
 
-// Unused dynamic LDS of a half-shard launch in a two-chain rollout (launch_step_geometric says why).  stages_rows: the kernel has its
+// Unused dynamic LDS of a half-shard launch in a two-chain rollout (step_geometric says why).  stages_rows: the kernel has its
 // static LDS block for the observation rows (or the segment tables), else only its 16-byte minimum.
 static size_t split_lds_pad(const mds_handle* h, bool stages_rows) {
   const size_t static_lds = stages_rows ? (size_t)kBlock * kObsDim * elem_size(h->cfg.dtype) : 16;
   return static_lds < kSplitLds ? kSplitLds - static_lds : 0;
 }
 
-// k_step over 256-drone batches [batch0, batch0 + nb) (nb == 0: the whole shard); half-shard launches of a two-stream rollout
-// are padded to 32 KB LDS like the fused step's (launch_step_geometric)
-static void launch_step_plain(mds_handle* h, const void* action, void* obs, hipStream_t st, unsigned batch0 = 0, unsigned nb = 0) {
+// One env.step of the batches ch covers: k_step; half-shard launches of a two-chain rollout are padded to 32 KB LDS like the fused
+// step's (step_geometric).  Ground effect / downwash handles (always one chain): one launch per substep, step_env_plain.
+// Like every step_* function below it only enqueues; the caller checks hipGetLastError once after its last launch.
+static int step_plain(mds_handle* h, const void* action, void* obs, const Chain& ch) {
+  hipStream_t st = ch.st;
+  if (h->envfx) return step_env_plain(h, action, obs, st, 0);
+  const unsigned batch0 = ch.i0, nb = ch.n;
   const dim3 grid(nb ? nb : (unsigned)((h->n + kBlock - 1) / kBlock));
   const size_t pad = nb ? split_lds_pad(h, obs != nullptr) : 0;
   with_flags([&](auto HAS_OBS, auto RK4, auto DRAG) {
@@ -702,6 +772,7 @@ static void launch_step_plain(mds_handle* h, const void* action, void* obs, hipS
                                                                                   (S*)h->state_lo);
     });
   }, obs != nullptr, h->cfg.integrator == MDS_INTEGRATOR_RK4, has_drag(h));
+  return MDS_OK;
 }
 
 // [UPSTREAM] BaseAviary.step under ground effect / downwash: one launch per physics substep on the double-buffered state
@@ -774,11 +845,8 @@ int mds_step(mds_handle* h, const void* action, void* obs, void* stream) {
   MDS_DEV(h);
   if (!h || !action) return fail(MDS_EINVAL, "mds_step: null argument");
   if (!aligned16(action) || !aligned16(obs)) return fail(MDS_EALIGN, "mds_step: action_dev/obs_dev");
-  hipStream_t st = (hipStream_t)stream;
-  if (h->envfx) return step_env_plain(h, action, obs, st, 0);
-  launch_step_plain(h, action, obs, st);
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  if (int rc = step_plain(h, action, obs, Chain{(hipStream_t)stream, 0, 0})) return rc;
+  return check_launches();
 }
 
 int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
@@ -880,13 +948,18 @@ int mds_set_wind(mds_handle* h, const double force_world[3]) {
   return MDS_OK;
 }
 
-// batch0 / nb: the range of 256-drone batches this launch covers (nb == 0: all of them)
-static int launch_step_geometric(mds_handle* h, double t, void* obs, void* act, hipStream_t st, unsigned batch0 = 0, unsigned nb = 0) {
+// One fused control step (trajectory sample -> GeometricControl -> env.step) of the 256-drone batches ch covers; ground effect /
+// downwash handles (always one chain): the controller with the first substep, then one launch per remaining substep (step_env_ctrl).
+static int step_geometric(mds_handle* h, double t, void* obs, void* act, const Chain& ch) {
+  hipStream_t st = ch.st;
+  if (h->envfx) return step_env_ctrl(h, 0, t, nullptr, 0.0, obs, act, st);
+  const unsigned batch0 = ch.i0, nb = ch.n;
   const unsigned nbatch = nb ? nb : (unsigned)((h->n + kBlock - 1) / kBlock);
-  // Half-shard launches of the two-stream rollout carry unused dynamic LDS up to 32 KB per workgroup: 5 workgroups per CU
-  // instead of 8.  A half then no longer fits the chip next to the other chain's half, so its workgroups enter as the other
-  // chain's retire and the two chains interleave from the first step on (C3: 15.6 -> 15.0 us per step over 20 000 steps,
-  // 16.5 -> 15.8 over 2000; on one stream the same padding costs 4 %, so full-shard launches do not get it).
+  // A chain that covers part of the shard (n != 0: a half, in a two-chain rollout) launches with unused dynamic LDS, so that its
+  // workgroups occupy kSplitLds = 32 KB each, static block included (split_lds_pad): 5 workgroups per CU instead of 8.  A half then
+  // no longer fits the chip next to the other chain's half, so its workgroups enter as the other chain's retire and the two chains
+  // interleave from the first step on (C3: 15.6 -> 15.0 us per step over 20 000 steps, 16.5 -> 15.8 over 2000; on one stream the
+  // same padding costs 4 %, so whole-shard launches do not get it).
   const size_t pad = nb ? split_lds_pad(h, h->traj_mode == 2 || obs) : 0;
   const dim3 grid(nbatch);
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
@@ -918,10 +991,8 @@ int mds_step_geometric(mds_handle* h, double t, void* obs, void* act, void* stre
   if (!h) return fail(MDS_EINVAL, "mds_step_geometric: null handle");
   if (!h->has_traj) return fail(MDS_ESTATE, "mds_step_geometric: call mds_set_lemniscate first");
   if (!aligned16(obs) || !aligned16(act)) return fail(MDS_EALIGN, "mds_step_geometric: obs_dev/action_dev");
-  if (h->envfx) return step_env_ctrl(h, 0, t, nullptr, 0.0, obs, act, (hipStream_t)stream);
-  launch_step_geometric(h, t, obs, act, (hipStream_t)stream);
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  if (int rc = step_geometric(h, t, obs, act, Chain{(hipStream_t)stream, 0, 0})) return rc;
+  return check_launches();
 }
 
 // One launch of the whole-rollout kernel: n_steps control steps with the state in registers.  ctrl: 0 GeometricControl, 1 LQRController
@@ -973,158 +1044,100 @@ int mds_rollout_geometric(mds_handle* h, double t0, int n_steps, void* obs, int 
   if (!h || n_steps < 0) return fail(MDS_EINVAL, "mds_rollout_geometric");
   if (!h->has_traj) return fail(MDS_ESTATE, "mds_rollout_geometric: call mds_set_lemniscate first");
   if (!aligned16(obs)) return fail(MDS_EALIGN, "mds_rollout_geometric: obs_dev");
+  hipStream_t st = (hipStream_t)stream;
   const double dt = 1.0 / h->cfg.ctrl_freq;
-  if (h->envfx) {          // ground effect / downwash: every substep is its own launch on the double-buffered state
-    h->last_rollout_streams = 1;
-    for (int k = 0; k < n_steps; ++k) {
-      if (int rc = step_env_ctrl(h, 0, t0, nullptr, 0.0, (obs_every_step || k == n_steps - 1) ? obs : nullptr, nullptr, (hipStream_t)stream)) return rc;
-      t0 += dt;
-    }
-    return MDS_OK;
-  }
   if (rollout_form_policy(h, n_steps) == 2) {
     // launch-bound shard sizes: the same loop through the whole-rollout kernel, rollout_chunk control steps per launch; every step's
     // observation overwrites obs (obs_every_step) exactly as the per-step loop's launches do, or only the last step's is written
     h->last_rollout_streams = 1;
     h->last_rollout_form = 2;
-    for (int k = 0; k < n_steps;) {
-      const int chunk = n_steps - k < h->rollout_chunk ? n_steps - k : h->rollout_chunk;
-      const bool last = k + chunk == n_steps;
-      launch_rollout_kernel(h, 0, t0, chunk, obs_every_step ? obs : nullptr, 0, (!obs_every_step && last) ? obs : nullptr, (hipStream_t)stream);
-      for (int j = 0; j < chunk; ++j) t0 += dt;        // t accumulates step by step, as inside the kernel and in the reference loop
-      k += chunk;
+    for (Chunks c{n_steps, h->rollout_chunk, t0, dt, 0, 0}; c.k < n_steps; c.advance(c.len())) {
+      const bool last = c.k + c.len() == n_steps;
+      launch_rollout_kernel(h, 0, c.t, c.len(), obs_every_step ? obs : nullptr, 0, (!obs_every_step && last) ? obs : nullptr, st);
     }
-    MDS_HIP(hipGetLastError());
+    return check_launches();
+  }
+  if (!h->envfx) h->last_rollout_form = 1;       // (ground effect / downwash handles have no launch form: they keep reporting 0)
+  // Drones never read each other's rows in this kernel, so the two halves of a big shard are two independent step chains.  Run on
+  // two streams they drift out of phase: one half's load/store bursts fill the other's compute phase (measured on C3: 17.5 ->
+  // 15.7-16.3 us per step).  The caller's stream orders both chains.
+  double t = t0;
+  auto step = [&](int k, const Chain* ch, int nc) -> int {
+    void* o = (obs_every_step || k == n_steps - 1) ? obs : nullptr;
+    for (int c = 0; c < nc; ++c)
+      if (int rc = step_geometric(h, t, o, nullptr, ch[c])) return rc;
+    t += dt;          // t accumulates exactly like the reference loop (t += env.CTRL_TIMESTEP, EnvGeometric.py:473)
     return MDS_OK;
-  }
-  h->last_rollout_form = 1;
-  const unsigned nbatch = (unsigned)((h->n + kBlock - 1) / kBlock);
-  const int streams = rollout_streams_policy(h, 0, n_steps);
-  if (streams == 2 && nbatch >= 2) {
-    // Drones never read each other's rows in this kernel, so the two halves of the shard are two independent step
-    // chains.  Run on two streams they drift out of phase: one half's load/store bursts fill the other's compute
-    // phase (measured on C3: 17.5 -> 15.7-16.3 us per step).  The caller's stream orders both chains.
-    hipStream_t st = (hipStream_t)stream, sb = h->split_st;
-    h->last_rollout_streams = 2;
-    const unsigned half = nbatch / 2;
-    auto body = [&]() -> int {
-      for (int k = 0; k < n_steps; ++k) {
-        void* o = (obs_every_step || k == n_steps - 1) ? obs : nullptr;
-        if (k == 0)
-          if (int rc = split_fork(h, st)) return rc;
-        launch_step_geometric(h, t0, o, nullptr, st, 0, half);
-        launch_step_geometric(h, t0, o, nullptr, sb, half, nbatch - half);
-        t0 += dt;
-      }
-      MDS_HIP(hipGetLastError());
-      return MDS_OK;
-    };
-    return split_join(h, st, body());
-  }
-  h->last_rollout_streams = 1;
-  for (int k = 0; k < n_steps; ++k) {
-    // t accumulates exactly like the reference loop (t += env.CTRL_TIMESTEP, EnvGeometric.py:473)
-    launch_step_geometric(h, t0, (obs_every_step || k == n_steps - 1) ? obs : nullptr, nullptr, (hipStream_t)stream);
-    t0 += dt;
-  }
-  MDS_HIP(hipGetLastError());
+  };
+  return step_loop_batches(h, st, 0, n_steps, step);
+}
+
+// what mds_rollout_step and mds_rollout_step_fused ask of their arguments
+static int rollout_step_args(const mds_handle* h, const char* who, const void* actions, int n_action_sets, int first_step, int n_steps,
+                             const void* obs_log, int log_slots, int episode_len) {
+  if (!h || !actions || n_action_sets < 1 || first_step < 0 || n_steps < 0 || (obs_log && log_slots < 1) || episode_len < 0)
+    return fail(MDS_EINVAL, who, ": arguments");
+  if (episode_len > 0 && !h->init_pose) return fail(MDS_ESTATE, who, ": episode resets need an earlier mds_reset");
+  const size_t es = elem_size(h->cfg.dtype), act_bytes = (size_t)h->n * 4 * es, obs_bytes = (size_t)h->n * kObsDim * es;
+  if (!aligned16(actions) || !aligned16(obs_log) || (n_action_sets > 1 && act_bytes % 16) || (obs_log && log_slots > 1 && obs_bytes % 16))
+    return fail(MDS_EALIGN, who, ": actions_dev/obs_log_dev (every action set and log slot must start 16-byte aligned)");
   return MDS_OK;
 }
 
 int mds_rollout_step(mds_handle* h, const void* actions, int n_action_sets, int first_step, int n_steps, void* obs_log, int log_slots,
                      int episode_len, void* stream) {
   MDS_DEV(h);
-  if (!h || !actions || n_action_sets < 1 || first_step < 0 || n_steps < 0 || (obs_log && log_slots < 1) || episode_len < 0)
-    return fail(MDS_EINVAL, "mds_rollout_step: arguments");
-  if (episode_len > 0 && !h->init_pose) return fail(MDS_ESTATE, "mds_rollout_step: episode resets need an earlier mds_reset");
+  if (int rc = rollout_step_args(h, "mds_rollout_step", actions, n_action_sets, first_step, n_steps, obs_log, log_slots, episode_len)) return rc;
   const size_t es = elem_size(h->cfg.dtype), act_bytes = (size_t)h->n * 4 * es, obs_bytes = (size_t)h->n * kObsDim * es;
-  if (!aligned16(actions) || !aligned16(obs_log) || (n_action_sets > 1 && act_bytes % 16) || (obs_log && log_slots > 1 && obs_bytes % 16))
-    return fail(MDS_EALIGN, "mds_rollout_step: actions_dev/obs_log_dev (every action set and log slot must start 16-byte aligned)");
-  hipStream_t st = (hipStream_t)stream;
-  if (h->envfx) {          // ground effect / downwash: the env.step loop, one launch per substep
-    h->last_rollout_streams = 1;
-    for (int k = 0; k < n_steps; ++k) {
-      const long long j = (long long)first_step + k;
-      if (episode_len > 0 && j > 0 && j % episode_len == 0)
-        if (int rc = launch_reset_range(h, st, 0, h->n)) return rc;
-      const char* a = (const char*)actions + (size_t)(j % n_action_sets) * act_bytes;
-      char* o = obs_log ? (char*)obs_log + (size_t)(j % log_slots) * obs_bytes : nullptr;
-      if (int rc = step_env_plain(h, a, o, st, 0)) return rc;
-    }
-    return MDS_OK;
-  }
-  const unsigned nbatch = (unsigned)((h->n + kBlock - 1) / kBlock);
-  const bool split = rollout_streams_policy(h, 0, n_steps) == 2 && nbatch >= 2;
-  const unsigned half = nbatch / 2;
-  if (split)         // the two halves of the shard as independent step chains, as in mds_rollout_geometric
-    if (int rc = split_fork(h, st)) return rc;
-  h->last_rollout_streams = split ? 2 : 1;
-  auto body = [&]() -> int {
-    for (int k = 0; k < n_steps; ++k) {
-      const long long j = (long long)first_step + k;
-      const char* a = (const char*)actions + (size_t)(j % n_action_sets) * act_bytes;
-      char* o = obs_log ? (char*)obs_log + (size_t)(j % log_slots) * obs_bytes : nullptr;
-      if (episode_len > 0 && j > 0 && j % episode_len == 0) {      // a new episode starts at step j: back to the initial poses
-        const size_t mid = (size_t)half * kBlock;
-        if (split) {
-          if (int rc = launch_reset_range(h, st, 0, mid)) return rc;
-          if (int rc = launch_reset_range(h, h->split_st, mid, h->n)) return rc;
-        } else if (int rc = launch_reset_range(h, st, 0, h->n)) {
-          return rc;
-        }
+  // the two halves of a big shard as independent step chains, as in mds_rollout_geometric
+  auto step = [&](int k, const Chain* ch, int nc) -> int {
+    const long long j = (long long)first_step + k;
+    const char* a = (const char*)actions + (size_t)(j % n_action_sets) * act_bytes;
+    char* o = obs_log ? (char*)obs_log + (size_t)(j % log_slots) * obs_bytes : nullptr;
+    if (episode_len > 0 && j > 0 && j % episode_len == 0)        // a new episode starts at step j: back to the initial poses
+      for (int c = 0; c < nc; ++c) {
+        const size_t i0 = (size_t)ch[c].i0 * kBlock, i1 = i0 + (size_t)ch[c].n * kBlock;
+        if (int rc = launch_reset_range(h, ch[c].st, i0, ch[c].n && i1 < (size_t)h->n ? i1 : (size_t)h->n)) return rc;
       }
-      if (split) {
-        launch_step_plain(h, a, o, st, 0, half);
-        launch_step_plain(h, a, o, h->split_st, half, nbatch - half);
-      } else {
-        launch_step_plain(h, a, o, st);
-      }
-    }
-    MDS_HIP(hipGetLastError());
+    for (int c = 0; c < nc; ++c)
+      if (int rc = step_plain(h, a, o, ch[c])) return rc;
     return MDS_OK;
   };
-  const int rc = body();
-  return split ? split_join(h, st, rc) : rc;
+  return step_loop_batches(h, (hipStream_t)stream, 0, n_steps, step);
 }
 
 int mds_rollout_step_fused(mds_handle* h, const void* actions, int n_action_sets, int first_step, int n_steps, void* obs_log,
                            int log_slots, int episode_len, int steps_per_launch, void* stream) {
   MDS_DEV(h);
-  if (!h || !actions || n_action_sets < 1 || first_step < 0 || n_steps < 0 || (obs_log && log_slots < 1) || episode_len < 0 ||
-      steps_per_launch < 1)
-    return fail(MDS_EINVAL, "mds_rollout_step_fused: arguments");
-  if (h->envfx)                 // env-mates interact every substep: no state-in-registers form; the step-by-step loop serves it
+  if (steps_per_launch < 1) return fail(MDS_EINVAL, "mds_rollout_step_fused: arguments");
+  if (h && h->envfx)            // env-mates interact every substep: no state-in-registers form; the step-by-step loop serves it
     return mds_rollout_step(h, actions, n_action_sets, first_step, n_steps, obs_log, log_slots, episode_len, stream);
-  if (episode_len > 0 && !h->init_pose) return fail(MDS_ESTATE, "mds_rollout_step_fused: episode resets need an earlier mds_reset");
-  const size_t es = elem_size(h->cfg.dtype), act_bytes = (size_t)h->n * 4 * es, obs_bytes = (size_t)h->n * kObsDim * es;
-  if (!aligned16(actions) || !aligned16(obs_log) || (n_action_sets > 1 && act_bytes % 16) || (obs_log && log_slots > 1 && obs_bytes % 16))
-    return fail(MDS_EALIGN, "mds_rollout_step_fused: actions_dev/obs_log_dev (every action set and log slot must start 16-byte aligned)");
+  if (int rc = rollout_step_args(h, "mds_rollout_step_fused", actions, n_action_sets, first_step, n_steps, obs_log, log_slots, episode_len))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid = grid_for(h->n, kBlock);
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-  long long j = first_step;
-  const long long j_end = (long long)first_step + n_steps;
-  while (j < j_end) {
-    if (episode_len > 0 && j > 0 && j % episode_len == 0)
-      if (int rc = launch_reset_range(h, st, 0, h->n)) return rc;
-    long long chunk = j_end - j < steps_per_launch ? j_end - j : steps_per_launch;
-    if (episode_len > 0) {                                  // a launch never crosses an episode boundary
-      const long long to_boundary = episode_len - j % episode_len;
-      if (chunk > to_boundary) chunk = to_boundary;
+  int ks = 0;
+  for (Chunks c{n_steps, steps_per_launch, 0.0, 0.0, obs_log ? first_step % log_slots : 0, obs_log ? log_slots : 0}; c.k < n_steps; c.advance(ks)) {
+    const long long j = (long long)first_step + c.k;
+    ks = c.len();
+    if (episode_len > 0) {
+      if (j > 0 && j % episode_len == 0)
+        if (int rc = launch_reset_range(h, st, 0, h->n)) return rc;
+      const long long to_boundary = episode_len - j % episode_len;        // a launch never crosses an episode boundary
+      if (ks > to_boundary) ks = (int)to_boundary;
     }
-    const int a0 = (int)(j % n_action_sets), s0 = obs_log ? (int)(j % log_slots) : 0;
+    const int a0 = (int)(j % n_action_sets), s0 = c.slot;
     with_flags([&](auto RK4, auto DRAG) {
       with_dtype(h->cfg.dtype, [&](auto DT) {
         using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
         k_rollout_step<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(params<T>(h).c, h->n, h->ld, (S*)h->state, (const T*)h->origin, (T*)rpm_track(h),
                                                                      (const S*)actions, a0, n_action_sets, (S*)obs_log, s0, obs_log ? log_slots : 1,
-                                                                     (int)chunk, (S*)h->state_lo);
+                                                                     ks, (S*)h->state_lo);
       });
     }, rk4, drag);
-    j += chunk;
   }
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  return check_launches();
 }
 
 int mds_set_rollout_streams(mds_handle* h, int n_streams) {
@@ -1166,48 +1179,47 @@ int mds_get_last_rollout_form(const mds_handle* h) {
 // ctrl: 0 GeometricControl, 1 LQRController (12-state), 2 LQROmegaController + ThrustOmega, 3 LQRYankOmegaController + YankOmega
 int rollout_fused(mds_handle* h, double t0, int n_steps, void* obs_log, void* obs_last, void* stream, int ctrl, const char* who) {
   if (!h || n_steps < 0) return fail(MDS_EINVAL, who);
-  if (h->envfx) {
-    // ground effect / downwash: env-mates interact every physics substep, so there is no state-in-registers form; the same loop
-    // runs step by step (one launch per substep), each step's observation written straight into its slot of the log
-    if (!h->has_traj) return fail(MDS_ESTATE, "mds_rollout_*_fused: call mds_set_lemniscate first");
-    if (ctrl == 1 && !h->has_lqr12) return fail(MDS_ESTATE, "mds_rollout_lqr_fused: call mds_set_lqr_gain first");
-    if (ctrl >= 2 && !obs_last) return fail(MDS_EINVAL, "mds_rollout_nominal_fused: obs_dev is required (in: current observation, out: last one)");
-    if (!aligned16(obs_log) || !aligned16(obs_last)) return fail(MDS_EALIGN, "mds_rollout_*_fused: obs buffers");
-    const size_t obs_bytes = (size_t)h->n * kObsDim * elem_size(h->cfg.dtype);
-    const double dt = 1.0 / h->cfg.ctrl_freq;
-    hipStream_t st = (hipStream_t)stream;
-    for (int k = 0; k < n_steps; ++k) {
-      char* slot = obs_log ? (char*)obs_log + (size_t)k * obs_bytes : nullptr;
-      const bool last = k == n_steps - 1;
-      if (ctrl <= 1) {
-        void* o = slot ? (void*)slot : (last ? obs_last : nullptr);
-        if (int rc = step_env_ctrl(h, ctrl, t0, nullptr, 0.0, o, nullptr, st)) return rc;
-        if (slot && last && obs_last) MDS_HIP(hipMemcpyAsync(obs_last, slot, obs_bytes, hipMemcpyDeviceToDevice, st));
-      } else {
-        if (int rc = step_nominal_lowlevel(h, t0, obs_last, nullptr, nullptr, stream, false, who, nullptr, false, false, 0.0)) return rc;
-        if (slot) MDS_HIP(hipMemcpyAsync(slot, obs_last, obs_bytes, hipMemcpyDeviceToDevice, st));
-      }
-      t0 += dt;
-    }
-    return MDS_OK;
-  }
   if (!h->has_traj) return fail(MDS_ESTATE, "mds_rollout_*_fused: call mds_set_lemniscate first");
-  const bool lqr = ctrl == 1;
-  if (lqr && !h->has_lqr12) return fail(MDS_ESTATE, "mds_rollout_lqr_fused: call mds_set_lqr_gain first");
+  if (ctrl == 1 && !h->has_lqr12) return fail(MDS_ESTATE, "mds_rollout_lqr_fused: call mds_set_lqr_gain first");
   if (ctrl >= 2) {
-    if (h->traj_mode != 1) return fail(MDS_EUNSUPPORTED, "mds_rollout_nominal_fused: Lemniscate trajectories only (use mds_step_nominal)");
+    // (ground effect / downwash handles go step by step, below: what their step function does not serve it refuses itself)
+    if (h->traj_mode != 1 && !h->envfx) return fail(MDS_EUNSUPPORTED, "mds_rollout_nominal_fused: Lemniscate trajectories only (use mds_step_nominal)");
     if (h->cfg.dtype == MDS_F16) return fail(MDS_EUNSUPPORTED, "mds_rollout_nominal_fused: fp16 storage");
     if (!obs_last) return fail(MDS_EINVAL, "mds_rollout_nominal_fused: obs_dev is required (in: current observation, out: last one)");
   }
   if (!aligned16(obs_log) || !aligned16(obs_last)) return fail(MDS_EALIGN, "mds_rollout_*_fused: obs buffers");
   // step k's rows start n * 20 elements behind step k - 1's and go out in 16-byte chunks: fp16 storage with an odd n is the one case
   // in which a slot of the log can start off a 16-byte boundary
-  if (obs_log && n_steps > 1 && ((size_t)h->n * kObsDim * elem_size(h->cfg.dtype)) % 16)
+  const size_t obs_bytes = (size_t)h->n * kObsDim * elem_size(h->cfg.dtype);
+  if (obs_log && n_steps > 1 && obs_bytes % 16)
     return fail(MDS_EALIGN, "mds_rollout_*_fused: obs_log_dev (every action set and log slot must start 16-byte aligned)");
+  hipStream_t st = (hipStream_t)stream;
+  if (h->envfx) {
+    // ground effect / downwash: env-mates interact every physics substep, so there is no state-in-registers form; the same loop
+    // runs step by step (one launch per substep), each step's observation written straight into its slot of the log
+    const double dt = 1.0 / h->cfg.ctrl_freq;
+    const int streams_before = h->last_rollout_streams;          // (not one of the calls mds_get_last_rollout_streams reports)
+    auto step = [&](int k, const Chain* ch, int) -> int {
+      char* slot = obs_log ? (char*)obs_log + (size_t)k * obs_bytes : nullptr;
+      const bool last = k == n_steps - 1;
+      if (ctrl <= 1) {
+        void* o = slot ? (void*)slot : (last ? obs_last : nullptr);
+        if (int rc = ctrl == 0 ? step_geometric(h, t0, o, nullptr, ch[0]) : step_lqr(h, t0, o, nullptr, st)) return rc;
+        if (slot && last && obs_last) MDS_HIP(hipMemcpyAsync(obs_last, slot, obs_bytes, hipMemcpyDeviceToDevice, st));
+      } else {
+        if (int rc = step_nominal_lowlevel(h, t0, obs_last, nullptr, nullptr, st)) return rc;
+        if (slot) MDS_HIP(hipMemcpyAsync(slot, obs_last, obs_bytes, hipMemcpyDeviceToDevice, st));
+      }
+      t0 += dt;
+      return MDS_OK;
+    };
+    const int rc = step_loop(h, st, 1, 0, 0, 0, n_steps, step);
+    h->last_rollout_streams = streams_before;
+    return rc;
+  }
   if (n_steps == 0) return MDS_OK;
-  launch_rollout_kernel(h, ctrl, t0, n_steps, obs_log, (size_t)h->n * kObsDim, obs_last, (hipStream_t)stream);
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  launch_rollout_kernel(h, ctrl, t0, n_steps, obs_log, (size_t)h->n * kObsDim, obs_last, st);
+  return check_launches();
 }
 
 int mds_rollout_geometric_fused(mds_handle* h, double t0, int n_steps, void* obs_log, void* obs_last, void* stream) {
@@ -1429,11 +1441,6 @@ int mds_cbf_rows(mds_handle* h, const void* x, const void* xdes, void* G, void* 
   return MDS_OK;
 }
 
-// envs [e0, e0 + ne) of the batch; slot selects the cost-class tables (0: whole batch, 1 / 2: halves of a two-stream rollout)
-struct EnvRange {
-  int e0, ne, slot;
-};
-
 static int cbf_filter_range(mds_handle* h, const void* obs_, const void* xdes_, const void* unom_, void* usafe_, int32_t* status_,
                             void* stream, EnvRange rg) {
   hipStream_t st = (hipStream_t)stream;
@@ -1569,18 +1576,16 @@ static void launch_dslpid(mds_handle* h, bool step, const void* obs_in, const vo
   else launch(std::false_type{}, std::false_type{}, std::false_type{});         // the controller alone integrates nothing: one instantiation
 }
 
-// one MultiDroneEnv.sim_step for the batches [batch0, batch0 + nb) (nb == 0: the whole shard)
-static void launch_step_dslpid(mds_handle* h, const void* tpos, const void* trpy, void* obs, void* act, hipStream_t st, unsigned batch0 = 0,
-                               unsigned nb = 0) {
-  launch_dslpid(h, true, nullptr, tpos, trpy, obs, act, st, batch0, nb);
-}
-
-// the same step under ground effect / downwash: the controller reads the handle's state and leaves the action in act_scratch (or the
-// caller's buffer), then env.step runs it one substep per launch
-static int step_env_dslpid(mds_handle* h, const void* tpos, const void* trpy, void* obs, void* act_out, hipStream_t st) {
-  void* act = act_out ? act_out : h->act_scratch;
-  launch_dslpid(h, false, nullptr, tpos, trpy, nullptr, act, st);
-  return step_env_plain(h, act, obs, st, 0);
+// One MultiDroneEnv.sim_step of the batches ch covers.  Ground effect / downwash handles (always one chain): the controller reads the
+// handle's state and leaves the action in act_scratch (or the caller's buffer), then env.step runs it one substep per launch.
+static int step_dslpid(mds_handle* h, const void* tpos, const void* trpy, void* obs, void* act, const Chain& ch) {
+  if (h->envfx) {
+    if (!act) act = h->act_scratch;
+    launch_dslpid(h, false, nullptr, tpos, trpy, nullptr, act, ch.st);
+    return step_env_plain(h, act, obs, ch.st, 0);
+  }
+  launch_dslpid(h, true, nullptr, tpos, trpy, obs, act, ch.st, ch.i0, ch.n);
+  return MDS_OK;
 }
 
 int mds_dslpid_compute(mds_handle* h, const void* obs_in, const void* tpos, const void* trpy, void* act, void* stream) {
@@ -1596,10 +1601,8 @@ int mds_step_dslpid(mds_handle* h, const void* tpos, const void* trpy, void* obs
   MDS_DEV(h);
   if (!h || !tpos || !trpy) return fail(MDS_EINVAL, "mds_step_dslpid: null argument");
   if (!aligned16(obs) || !aligned16(act)) return fail(MDS_EALIGN, "mds_step_dslpid: obs_dev/action_dev");
-  if (h->envfx) return step_env_dslpid(h, tpos, trpy, obs, act, (hipStream_t)stream);
-  launch_step_dslpid(h, tpos, trpy, obs, act, (hipStream_t)stream);
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  if (int rc = step_dslpid(h, tpos, trpy, obs, act, Chain{(hipStream_t)stream, 0, 0})) return rc;
+  return check_launches();
 }
 
 int mds_rollout_dslpid(mds_handle* h, const void* tpos, const void* trpy, int n_target_sets, int first_step, int n_steps, void* obs,
@@ -1607,48 +1610,16 @@ int mds_rollout_dslpid(mds_handle* h, const void* tpos, const void* trpy, int n_
   MDS_DEV(h);
   if (!h || !tpos || !trpy || n_target_sets < 1 || first_step < 0 || n_steps < 0) return fail(MDS_EINVAL, "mds_rollout_dslpid: arguments");
   if (!aligned16(obs)) return fail(MDS_EALIGN, "mds_rollout_dslpid: obs_dev");
-  hipStream_t st = (hipStream_t)stream;
   const size_t set_bytes = (size_t)h->n * 3 * elem_size(h->cfg.dtype);
-  auto targets = [&](int k, const void** p, const void** r) {
+  // the PID memory is per drone too: the two halves of a big shard are two independent chains, as in mds_rollout_geometric
+  auto step = [&](int k, const Chain* ch, int nc) -> int {
     const size_t off = (size_t)(((long long)first_step + k) % n_target_sets) * set_bytes;
-    *p = (const char*)tpos + off;
-    *r = (const char*)trpy + off;
-  };
-  const void *p, *r;
-  if (h->envfx) {
-    h->last_rollout_streams = 1;
-    for (int k = 0; k < n_steps; ++k) {
-      targets(k, &p, &r);
-      if (int rc = step_env_dslpid(h, p, r, (obs_every_step || k == n_steps - 1) ? obs : nullptr, nullptr, st)) return rc;
-    }
+    void* o = (obs_every_step || k == n_steps - 1) ? obs : nullptr;
+    for (int c = 0; c < nc; ++c)
+      if (int rc = step_dslpid(h, (const char*)tpos + off, (const char*)trpy + off, o, nullptr, ch[c])) return rc;
     return MDS_OK;
-  }
-  const unsigned nbatch = (unsigned)((h->n + kBlock - 1) / kBlock);
-  if (rollout_streams_policy(h, 0, n_steps) == 2 && nbatch >= 2) {   // the PID memory is per drone too: two independent chains
-    hipStream_t sb = h->split_st;
-    h->last_rollout_streams = 2;
-    const unsigned half = nbatch / 2;
-    auto body = [&]() -> int {
-      for (int k = 0; k < n_steps; ++k) {
-        void* o = (obs_every_step || k == n_steps - 1) ? obs : nullptr;
-        targets(k, &p, &r);
-        if (k == 0)
-          if (int rc = split_fork(h, st)) return rc;
-        launch_step_dslpid(h, p, r, o, nullptr, st, 0, half);
-        launch_step_dslpid(h, p, r, o, nullptr, sb, half, nbatch - half);
-      }
-      MDS_HIP(hipGetLastError());
-      return MDS_OK;
-    };
-    return split_join(h, st, body());
-  }
-  h->last_rollout_streams = 1;
-  for (int k = 0; k < n_steps; ++k) {
-    targets(k, &p, &r);
-    launch_step_dslpid(h, p, r, (obs_every_step || k == n_steps - 1) ? obs : nullptr, nullptr, st);
-  }
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  };
+  return step_loop_batches(h, (hipStream_t)stream, 0, n_steps, step);
 }
 
 int mds_set_lqr_omega_gain(mds_handle* h, const double K[36]) {
@@ -1704,14 +1675,9 @@ int mds_lqr_compute(mds_handle* h, const void* obs, const void* des, void* u, vo
   return MDS_OK;
 }
 
-int mds_step_lqr(mds_handle* h, double t, void* obs, void* act, void* stream) {
-  MDS_DEV(h);
-  if (!h) return fail(MDS_EINVAL, "mds_step_lqr: null handle");
-  if (!h->has_traj) return fail(MDS_ESTATE, "mds_step_lqr: call mds_set_lemniscate / mds_set_trajectory_segments first");
-  if (!h->has_lqr12) return fail(MDS_ESTATE, "mds_step_lqr: call mds_set_lqr_gain first");
-  if (!aligned16(obs) || !aligned16(act)) return fail(MDS_EALIGN, "mds_step_lqr: obs_dev/action_dev");
-  if (h->envfx) return step_env_ctrl(h, 1, t, nullptr, 0.0, obs, act, (hipStream_t)stream);
-  hipStream_t st = (hipStream_t)stream;
+// one control step of the 12-state LQR (trajectory sample -> LQRController -> env.step) on the whole shard
+int step_lqr(mds_handle* h, double t, void* obs, void* act, hipStream_t st) {
+  if (h->envfx) return step_env_ctrl(h, 1, t, nullptr, 0.0, obs, act, st);
   const dim3 grid = grid_for(h->n, kBlock);
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
   with_flags([&](auto RK4, auto DRAG) {
@@ -1722,8 +1688,17 @@ int mds_step_lqr(mds_handle* h, double t, void* obs, void* act, void* stream) {
                                                                (T*)rpm_track(h), (S*)obs, (S*)act, (S*)h->state_lo);
     });
   }, rk4, drag);
-  MDS_HIP(hipGetLastError());
   return MDS_OK;
+}
+
+int mds_step_lqr(mds_handle* h, double t, void* obs, void* act, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_step_lqr: null handle");
+  if (!h->has_traj) return fail(MDS_ESTATE, "mds_step_lqr: call mds_set_lemniscate / mds_set_trajectory_segments first");
+  if (!h->has_lqr12) return fail(MDS_ESTATE, "mds_step_lqr: call mds_set_lqr_gain first");
+  if (!aligned16(obs) || !aligned16(act)) return fail(MDS_EALIGN, "mds_step_lqr: obs_dev/action_dev");
+  if (int rc = step_lqr(h, t, obs, act, (hipStream_t)stream)) return rc;
+  return check_launches();
 }
 
 int mds_set_lqr_yank_omega_gain(mds_handle* h, const double K[40]) {
@@ -1831,16 +1806,13 @@ int mds_thrust_omega_from_rates(mds_handle* h, const void* u, const void* rates,
 
 // nominal controller -> [ECBF QP] -> low level -> env.step.  with_filter = false: the plain loops of
 // simulations/EnvGeometricOmega.py / EnvGeometricYankOmega.py (ctrl[j].compute(obs[j]) = LQR + low level, :314 / :319).
-// have_nominal: the previous step's low-level launch has already left this step's u_hat / xdes in the scratch (want_next of that call);
-// want_next: this step's low-level launch also computes the nominal input of the step at t_next (C rollout loops; nominal 0 / 1 only).
-int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, void* action, void* stream, bool with_filter,
-                          const char* who, const EnvRange* rgp, bool have_nominal, bool want_next, double t_next) {
-  EnvRange rg = rgp ? *rgp : EnvRange{0, -1, 0};
+// The C rollout loops chain the nominal input from step to step (NominalStep: have_nominal / want_next).
+int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, void* action, hipStream_t st, const NominalStep& o) {
+  EnvRange rg = o.range;
+  const bool with_filter = o.with_filter;
   if (!h->has_traj || h->traj_mode != 1) return fail(MDS_ESTATE, "mds_step_cbf_geometric / mds_step_nominal: call mds_set_lemniscate first");
   if (!aligned16(obs) || !aligned16(action)) return fail(MDS_EALIGN, "mds_step_cbf_geometric / mds_step_nominal: obs_dev/action_dev");
   const bool yank = h->cbf_nominal == 2;
-  (void)who;
-  hipStream_t st = (hipStream_t)stream;
   const size_t es = elem_size(h->cfg.dtype);
   // One-launch form (k_cbf_step): order 2, whole envs per wave (D | 64, D <= 16), explicit Euler without drag, nominal 0 / 1, no
   // action output.  Everything else takes the three launches below.
@@ -1885,7 +1857,7 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
   const dim3 grid = grid_for(i1 - i0, kBlock);
   // the hover force is subtracted from the nominal input only on the way into the filter (CBFTest.py:339, CBFTestOrd3.py:341)
   const double hover_sub = with_filter ? h->cfg.M * h->cfg.G : 0.0;
-  const bool skip_nominal = have_nominal && h->next_nom_ok[rg.slot] && h->next_nom_t[rg.slot] == t;
+  const bool skip_nominal = o.have_nominal && h->next_nom_ok[rg.slot] && h->next_nom_t[rg.slot] == t;
   h->next_nom_ok[rg.slot] = false;
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
   const void* nom_K = h->cbf_nominal == 1 ? h->gain_dev[1] : nullptr;
@@ -1927,7 +1899,7 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
   MDS_HIP(hipGetLastError());
   const void* u_ll = h->cbf_unom;
   if (with_filter) {
-    int rc = cbf_filter_range(h, obs, h->cbf_xdes, h->cbf_unom, h->cbf_usafe, status, stream, rg);
+    int rc = cbf_filter_range(h, obs, h->cbf_xdes, h->cbf_unom, h->cbf_usafe, status, st, rg);
     if (rc != MDS_OK) return rc;
     u_ll = h->cbf_usafe;
   }
@@ -1935,12 +1907,11 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
   const double ll_offset = (with_filter && !yank) ? h->cfg.M * h->cfg.G : 0.0;
   if (h->envfx)            // ground effect / downwash: low level + first substep, then the remaining substeps (whole batch, one stream)
     return step_env_ctrl(h, yank ? 3 : 2, t, u_ll, ll_offset, obs, action, st);
-  const bool next_on = want_next && !yank && h->cbf_nominal <= 1 && !action;
+  const bool next_on = o.want_next && !yank && h->cbf_nominal <= 1 && !action;
   h->next_nom_ok[rg.slot] = next_on;
-  h->next_nom_t[rg.slot] = t_next;
-  lowlevel(yank, u_ll, ll_offset, next_on, t_next, 0);
-  MDS_HIP(hipGetLastError());
-  return MDS_OK;
+  h->next_nom_t[rg.slot] = o.t_next;
+  lowlevel(yank, u_ll, ll_offset, next_on, o.t_next, 0);
+  return check_launches();
 }
 
 // what k_cbf_rollout covers (mds_rollout_cbf_geometric_fused; mds_cbf_set_step_kernel(h, 2))
@@ -1966,7 +1937,9 @@ int mds_step_cbf_geometric(mds_handle* h, double t, void* obs, int32_t* status, 
     for (int k = 0; k < 3; ++k) h->next_nom_ok[k] = false;
     return mds_rollout_cbf_geometric_fused(h, t, 1, 1, nullptr, 0, 0, obs, status, nullptr, stream);
   }
-  return step_nominal_lowlevel(h, t, obs, status, action, stream, true, "mds_step_cbf_geometric");
+  NominalStep o;
+  o.with_filter = true;
+  return step_nominal_lowlevel(h, t, obs, status, action, (hipStream_t)stream, o);
 }
 
 int mds_rollout_cbf_geometric(mds_handle* h, double t0, int n_steps, void* obs, int32_t* status, void* stream) {
@@ -1977,7 +1950,6 @@ int mds_rollout_cbf_geometric(mds_handle* h, double t0, int n_steps, void* obs, 
     h->last_rollout_streams = 1;
     return mds_rollout_cbf_geometric_fused(h, t0, n_steps, 25, nullptr, 0, 0, obs, status, nullptr, stream);
   }
-  const double dt = 1.0 / h->cfg.ctrl_freq;
   // The env halves are independent step chains (a barrier row couples drones of one env only).  On two streams one half's
   // QP kernel (latency / ALU bound) runs beside the other half's nominal and low-level kernels (memory bound).  The split
   // must fall on a 256-drone batch boundary; each half keeps its own cost classes for the longest-first dispatch.
@@ -1988,39 +1960,25 @@ int mds_rollout_cbf_geometric(mds_handle* h, double t0, int n_steps, void* obs, 
       e_mid = e;
       break;
     }
-  const int streams = rollout_streams_policy(h, 1, n_steps);
-  if (streams == 2 && e_mid > 0) {
-    if (int rc = mds_step_cbf_geometric(h, t0, obs, status, nullptr, stream)) return rc;   // validation, scratch; step 1 on the caller's stream
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = split_fork(h, st)) return rc;
-    h->last_rollout_streams = 2;
-    const EnvRange half[2] = {EnvRange{0, e_mid, 1}, EnvRange{e_mid, E - e_mid, 2}};
-    auto body = [&]() -> int {
-      double t = t0 + dt;
-      for (int k = 1; k < n_steps; ++k) {
-        // each chain's low-level launch of step k also computes the nominal input of its step k + 1 (next_nominal), so that
-        // from its second step on a chain is two launches per step: QP, low level
-        for (int s = 0; s < 2; ++s)
-          if (int rc = step_nominal_lowlevel(h, t, obs, status, nullptr, s == 0 ? st : h->split_st, true, "mds_rollout_cbf_geometric", &half[s],
-                                             k > 1, k < n_steps - 1, t + dt))
-            return rc;
-        t += dt;
-      }
-      return MDS_OK;
-    };
-    return split_join(h, st, body());
+  const double dt = 1.0 / h->cfg.ctrl_freq;
+  double t = t0;
+  if (n_steps > 0) {     // validation and scratch allocation: the first step is a plain one, whole batch, on the caller's stream
+    if (int rc = mds_step_cbf_geometric(h, t, obs, status, nullptr, stream)) return rc;
+    t += dt;
   }
-  h->last_rollout_streams = 1;
-  for (int k = 0; k < n_steps; ++k) {
-    if (k == 0) {
-      if (int rc = mds_step_cbf_geometric(h, t0, obs, status, nullptr, stream)) return rc;   // validation; plain first step
-    } else if (int rc = step_nominal_lowlevel(h, t0, obs, status, nullptr, stream, true, "mds_rollout_cbf_geometric", nullptr, k > 1,
-                                              k < n_steps - 1, t0 + dt)) {
-      return rc;
+  auto step = [&](int k, const Chain* ch, int nc) -> int {
+    // each chain's low-level launch of step k also computes the nominal input of its step k + 1 (next_nominal), so that
+    // from its second step on a chain is two launches per step: QP, low level
+    NominalStep o;
+    o.with_filter = true; o.have_nominal = k > 1; o.want_next = k < n_steps - 1; o.t_next = t + dt;
+    for (int c = 0; c < nc; ++c) {
+      o.range = ch[c].n ? EnvRange{(int)ch[c].i0, (int)ch[c].n, c + 1} : EnvRange{0, E, 0};
+      if (int rc = step_nominal_lowlevel(h, t, obs, status, nullptr, ch[c].st, o)) return rc;
     }
-    t0 += dt;
-  }
-  return MDS_OK;
+    t += dt;
+    return MDS_OK;
+  };
+  return step_loop(h, (hipStream_t)stream, rollout_streams_policy(h, 1, n_steps), (unsigned)e_mid, (unsigned)E, 1, n_steps, step);
 }
 
 int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int steps_per_launch, void* obs_log, int log_slots, int first_slot,
@@ -2050,11 +2008,10 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
     const double dt3 = 1.0 / h->cfg.ctrl_freq, hover_sub = h->cfg.M * h->cfg.G;      // the hover force is subtracted from the yank on the way into the filter (:341)
     void* rpm3 = rpm_track(h);
     h->cbf_last_step_kernel = 2;
-    int slot3 = first_slot;
-    double t3 = t0;
-    for (int k0 = 0; k0 < n_steps; k0 += steps_per_launch) {
-      const int ks = n_steps - k0 < steps_per_launch ? n_steps - k0 : steps_per_launch;
-      int32_t* slog = status_log ? status_log + (size_t)k0 * h->cfg.num_envs : nullptr;
+    for (Chunks c{n_steps, steps_per_launch, t0, dt3, first_slot, obs_log ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
+      const int ks = c.len(), slot3 = c.slot;
+      const double t3 = c.t;
+      int32_t* slog = status_log ? status_log + (size_t)c.k * h->cfg.num_envs : nullptr;
       with_dtype_no_half(h->cfg.dtype, [&](auto DT) {       // f32 / f64 (checked above)
         using T = typename decltype(DT)::T;
         const double tol = h->cbf.tol > 0 ? h->cbf.tol : (sizeof(T) == 8 ? 1e-12 : 1e-6);
@@ -2068,8 +2025,6 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
         else launch(std::integral_constant<int, 8>{}, std::integral_constant<int, 48>{});
       });
       MDS_HIP(hipGetLastError());
-      for (int j = 0; j < ks; ++j) t3 += dt3;
-      if (obs_log) slot3 = (slot3 + ks) % log_slots;
     }
     return MDS_OK;
   }
@@ -2102,11 +2057,11 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
       MDS_HIP(hipMalloc((void**)&stamps_dev, n_stamp * sizeof(unsigned long long) * ((n_steps + steps_per_launch - 1) / steps_per_launch)));
     }
   unsigned long long* const stamps_base = stamps_dev;
-  int slot = first_slot;
-  double t = t0;
-  for (int k0 = 0; k0 < n_steps; k0 += steps_per_launch) {
-    const int ks = n_steps - k0 < steps_per_launch ? n_steps - k0 : steps_per_launch;
-    int32_t* slog = status_log ? status_log + (size_t)k0 * h->cfg.num_envs : nullptr;
+  // (t advances on the host exactly as inside the kernel, one += per step, so that consecutive launches continue the same sequence)
+  for (Chunks c{n_steps, steps_per_launch, t0, dt, first_slot, obs_log ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
+    const int ks = c.len(), slot = c.slot;
+    const double t = c.t;
+    int32_t* slog = status_log ? status_log + (size_t)c.k * h->cfg.num_envs : nullptr;
     with_dtype_no_half(h->cfg.dtype, [&](auto DT) {         // f32 / f32c / f64 (roll_fused_applies)
       using T = typename decltype(DT)::T;
       const double tol = h->cbf.tol > 0 ? h->cbf.tol : (sizeof(T) == 8 ? 1e-12 : 1e-6);
@@ -2123,9 +2078,6 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
       });
     });
     MDS_HIP(hipGetLastError());
-    // t advances on the host exactly as inside the kernel (one += per step), so that consecutive launches continue the same sequence
-    for (int j = 0; j < ks; ++j) t += dt;
-    if (obs_log) slot = (slot + ks) % log_slots;
     if (stamps_dev) stamps_dev += n_stamp;
   }
   if (stamps_base) {
@@ -2168,7 +2120,7 @@ int mds_step_nominal(mds_handle* h, double t, void* obs, void* action, void* str
   // (212 B per drone-step instead of 392 B over two launches: 34 / 48 us -> 18 us at C3)
   if (!action && h->has_traj && h->traj_mode == 1 && !h->envfx)
     return rollout_fused(h, t, 1, nullptr, obs, stream, h->cbf_nominal == 2 ? 3 : 2, "mds_step_nominal");
-  return step_nominal_lowlevel(h, t, obs, nullptr, action, stream, false, "mds_step_nominal");
+  return step_nominal_lowlevel(h, t, obs, nullptr, action, (hipStream_t)stream);
 }
 
 

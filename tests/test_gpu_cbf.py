@@ -1233,3 +1233,49 @@ def test_order3_degenerate_envs_do_not_run_to_the_iteration_cap(mds):
         assert (st.cpu().numpy() == 1).all() and it.max() < 100, (dtype, st, it)
         np.testing.assert_allclose(us.double().cpu().numpy(), unom, atol=1e-6)
         env.close()
+
+
+def test_chunked_rollouts_leave_no_seam_between_launches(mds):
+    """The rollouts that run several control steps per launch give, bit for bit, the same results however a call is cut into launches: the
+    time handed to each launch (one += dt per step), its slot of the log ring, and which launch is the last one.
+    Form 2 of rollout_geometric, 3 x 5 drones, 10 steps as 4 + 4 + 2 against one launch, every step's observation written or only the
+    last launch's last one; the persistent CBF rollout, 2 x 4 drones, 7 steps as 3 + 3 + 1 against one launch into a 4-slot ring."""
+    torch = mds.torch
+    xyz, rpy, P = H.c2_setup(3, 5, phase="c3")
+    for dtype in ("float32", "float64"):
+        for every in (True, False):
+            res = []
+            for per in (4, 16):
+                env = mds.CtrlAviary(drone_model=mds.DroneModel.CF2P, num_drones=5, initial_xyzs=xyz, initial_rpys=rpy, physics=mds.Physics.DYN,
+                                     pyb_freq=100, ctrl_freq=100, num_envs=3, dtype=dtype)
+                env.set_trajectories(P)
+                before = env.step(torch.zeros((3, 5, 4), dtype=env.dtype, device=env.device))[0].cpu().numpy().copy()
+                env.set_rollout_form(2, per)
+                o = env.rollout_geometric(0.0, 10, obs_every_step=every).cpu().numpy().copy()
+                assert env.last_rollout_form() == 2 and not np.array_equal(o, before)
+                res.append((o, env.get_state()))
+                env.close()
+            np.testing.assert_array_equal(res[0][0], res[1][0], err_msg=f"{dtype} obs_every_step={every}")
+            np.testing.assert_array_equal(res[0][1], res[1][1], err_msg=f"{dtype} obs_every_step={every}")
+    E, D, steps, slots = 2, 4, 7, 4
+    xyz, rpy, P = H.c2_setup(E, D, phase="c3", offset=1.0)
+    P[..., 4] = 0.5 + 0.15 * np.arange(D)                         # 15 cm apart: closer than the pair distance, rows go active
+    xyz[..., 2] = 0.5 + 0.3 * np.arange(D)
+    x_obs, obs_r = [np.array([[0.3, 0.2, 0.9], [0, 0, 0]])], [0.1]
+    res = []
+    for spl in (3, 7):
+        env = mds.CtrlAviary(drone_model=mds.DroneModel.CF2P, num_drones=D, initial_xyzs=xyz, initial_rpys=rpy, physics=mds.Physics.DYN,
+                             pyb_freq=100, ctrl_freq=100, num_envs=E, dtype="float32")
+        env.set_trajectories(P)
+        cbf = mds.DroneCBF(env, [mds.LinearizedOmegaModel(env) for _ in range(D)], safety_radius=0.1, zscale=1.0, order=2)
+        trk = mds.DroneQPTracker(cbf, num_robots=D, xdim=9, env=env)
+        env.step(torch.zeros((E, D, 4), dtype=env.dtype))
+        ring = torch.full((slots, E, D, 20), float("nan"), dtype=env.dtype, device=env.device)
+        slog = torch.full((steps, E), -1, dtype=torch.int32, device=env.device)
+        o, st = env.rollout_cbf_geometric_fused(0.0, steps, trk, x_obs, obs_r, steps_per_launch=spl, obs_log=ring, first_slot=1, status_log=slog)
+        res.append((env.get_state(), ring.cpu().numpy().copy(), o.cpu().numpy().copy(), slog.cpu().numpy().copy(), st.cpu().numpy().copy()))
+        env.close()
+    assert np.isfinite(res[1][1]).all() and (res[1][3] >= 0).all()
+    np.testing.assert_array_equal(res[1][2], res[1][1][(1 + steps - 1) % slots])       # the last observation is the ring's last slot
+    for a, b in zip(res[0], res[1]):
+        np.testing.assert_array_equal(a, b)
