@@ -1153,16 +1153,12 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 && R == 4) ? 4 : 1) void k_cbf_
     u[1] = conv ? m_clamp(un[1], -P.umax[1], P.umax[1]) : un[1];
     u[2] = conv ? m_clamp(un[2], -P.umax[2], P.umax[2]) : un[2];
     u[3] = conv ? m_clamp(un[3], -P.umax[3], P.umax[3]) : un[3];
-    LowLevelState<T> L;
-    L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-    L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
+    LowLevelState<T> L = load_lowlevel(ll, ld, i);
     T act4[4], prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4];
     thrust_omega_control(c, ctrl_dt, u, in2.s.w, L, act4);
-    ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-    ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
+    store_lowlevel(ll, ld, i, L);
     aviary_step_any<T, false, false, COMP>(c, in2.s, in2.r, act4, prev, clipped);
-    if (last_rpm)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+    store_last_rpm<false>(last_rpm, ld, i, clipped);
     pack_obs(in2.s, V3<T>{in2.P.cx, in2.P.cy, in2.P.cz}, clipped, o);
   }
   write_obs_rows<T, T>(raw, obs, n_end, i, valid, o);
@@ -1840,9 +1836,7 @@ __global__ __launch_bounds__(64) void k_cbf_rollout_o3(const Consts<T> c, const 
   const size_t n = (size_t)E * D;
   GeoIn<T> in;
   load_geo_in<T, T>(state, lem, ld, i, in);
-  LowLevelState<T> L;
-  L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-  L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
+  LowLevelState<T> L = load_lowlevel(ll, ld, i);
   T clipped[4];
   load4<T, T>(obs_io + i * kObsDim + 16, clipped);
   const V3<T> centre = {in.P.cx, in.P.cy, in.P.cz};
@@ -1901,10 +1895,8 @@ __global__ __launch_bounds__(64) void k_cbf_rollout_o3(const Consts<T> c, const 
   }
   if (drone) {
     store_state<T, T>(state, ld, i, in.s);
-    ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-    ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
-    if (last_rpm != nullptr && n_steps > 0)
-      for (int j = 0; j < 4; ++j) last_rpm[j * ld + i] = clipped[j];
+    store_lowlevel(ll, ld, i, L);
+    if (n_steps > 0) store_last_rpm<false>(last_rpm, ld, i, clipped);
   }
 }
 

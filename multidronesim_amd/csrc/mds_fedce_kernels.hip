@@ -115,8 +115,10 @@ __global__ __launch_bounds__(kFedceBlock) void k_fedce_identify(const Consts<T> 
   if (i >= n) return;                        // whole 16-lane rows leave together
   State<T> s;
   load_state<S, T>(state, ld, i, s);
-  const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+  const V3<T> org = load_origin(origin, ld, i);
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
+  // (the RPM planes in place here and at the end, not through load_prev_rpm / store_last_rpm as in k_fedce_omega_identify: with the
+  // helpers this kernel's instructions come out in another order, and its assembly is pinned)
   if (DRAG)
     for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
   FedceDes xd = {0.0, 0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
@@ -238,7 +240,9 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_rollout(const Consts<T> c,
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
   if (valid) {
     load_state<S, T>(state, ld, i, s);
-    org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+    org = load_origin(origin, ld, i);
+    // (the trajectory and the RPM planes in place, not through load_traj / sample_traj / load_prev_rpm as in k_dlqr_omega_rollout: with the
+    // helpers this kernel's and k_fedce_identify's instructions come out in another order, and their assembly is pinned)
     if (traj_mode == 1)
       P = {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)], lem[lidx(5, i, ld)],
            lem[lidx(6, i, ld)]};
@@ -298,8 +302,7 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_compute(const Consts<T> c,
     const S* d = des + i * 11;
     T e[12];
     const V3<T> perr = {(T)o[0] - (T)d[0], (T)o[1] - (T)d[1], (T)o[2] - (T)d[2]};
-    lqr12_error<T>(V3<T>{(T)o[7], (T)o[8], (T)o[9]}, V3<T>{(T)o[13], (T)o[14], (T)o[15]}, V3<T>{(T)o[10], (T)o[11], (T)o[12]}, perr,
-                   V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], (T)d[10], e);
+    lqr12_error<T>(obs_rpy<T>(o), obs_ang_vel<T>(o), obs_vel<T>(o), perr, V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], (T)d[10], e);
     for (int k = 0; k < 12; ++k) se[threadIdx.x][k] = e[k];
   }
   __syncthreads();

@@ -58,15 +58,6 @@ template <typename T> __device__ __forceinline__ void omega_error(const State<T>
                        p - xd.p, xd.v, xd.yaw, e);
 }
 
-template <typename T> __device__ __forceinline__ void ll_load(const T* __restrict__ ll, size_t ld, size_t i, LowLevelState<T>& L) {
-  L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-  L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
-}
-template <typename T> __device__ __forceinline__ void ll_store(T* __restrict__ ll, size_t ld, size_t i, const LowLevelState<T>& L) {
-  ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-  ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
-}
-
 // One warm-up or exploration phase of fedCE_iteration (EnvGeometricOmega.py:143-193, :226-262) for every drone, n_steps steps, wind from
 // Consts.  Per step: e_t, the raw u through compute_low_level (body rate = the state's; the PID memory from / to ll), phi = [e_t,
 // max(u0, 0) - M G, u1..3] (computeControlFromInput clips u[0] in place, :93), the step, e_{t+1} and -- update 1: every step; 2: every
@@ -89,12 +80,10 @@ __global__ __launch_bounds__(kFedceBlock) void k_fedce_omega_identify(const Cons
   const bool live = r < R;
   State<T> s;
   load_state<S, T>(state, ld, i, s);
-  const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+  const V3<T> org = load_origin(origin, ld, i);
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
-  if (DRAG)
-    for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-  LowLevelState<T> L;
-  ll_load<T>(ll, ld, i, L);
+  load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
+  LowLevelState<T> L = load_lowlevel(ll, ld, i);
   OmegaDes xd = {0.0, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
   if (xdes) {
     const double* x = xdes + (size_t)i * M;
@@ -155,10 +144,9 @@ __global__ __launch_bounds__(kFedceBlock) void k_fedce_omega_identify(const Cons
   }
   if (r == 0) {
     store_state<S, T>(state, ld, i, s);
-    ll_store<T>(ll, ld, i, L);
+    store_lowlevel(ll, ld, i, L);
     if (status && bits) status[i] |= bits;
-    if (last_rpm && n_steps > 0)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = DRAG ? prev[k] : clipped[k];
+    if (last_rpm && n_steps > 0) store_last_rpm<DRAG>(last_rpm, ld, i, DRAG ? prev : clipped);
   }
 }
 
@@ -209,20 +197,15 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_omega_rollout(const Consts
   L.last_omega = L.integral = {T(0), T(0), T(0)};
   if (valid) {
     load_state<S, T>(state, ld, i, s);
-    org = {origin[i], origin[ld + i], origin[2 * ld + i]};
-    if (traj_mode == 1)
-      P = {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)], lem[lidx(5, i, ld)],
-           lem[lidx(6, i, ld)]};
-    else
-      ti = traj_info(tinfo, i);
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    ll_load<T>(ll, ld, i, L);
+    org = load_origin(origin, ld, i);
+    load_traj(traj_mode, lem, tinfo, ld, i, P, ti);
+    load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
+    L = load_lowlevel(ll, ld, i);
   }
   const T(*my_env)[M] = se + le * D;
   for (int step = 0; step < n_steps; ++step) {
     if (valid) {
-      const Desired<T> des = traj_mode == 1 ? lemniscate_local(P, t) : TrajLocal<T>::eval(segs, ti, t, org);
+      const Desired<T> des = sample_traj(traj_mode, P, segs, ti, t, org);
       T e[M];
       error_state9<T>(euler_from_quat(s.q), s.v, s.p - des.p, des.v, des.yaw, e);
       for (int k = 0; k < M; ++k) se[threadIdx.x][k] = e[k];
@@ -248,9 +231,8 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_omega_rollout(const Consts
   }
   if (valid) {
     store_state<S, T>(state, ld, i, s);
-    ll_store<T>(ll, ld, i, L);
-    if (last_rpm && n_steps > 0)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = DRAG ? prev[k] : clipped[k];
+    store_lowlevel(ll, ld, i, L);
+    if (last_rpm && n_steps > 0) store_last_rpm<DRAG>(last_rpm, ld, i, DRAG ? prev : clipped);
   }
 }
 
@@ -274,7 +256,7 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_omega_compute(const Consts
     const S* d = des + i * 11;
     T e[M];
     const V3<T> perr = {(T)o[0] - (T)d[0], (T)o[1] - (T)d[1], (T)o[2] - (T)d[2]};
-    error_state9<T>(V3<T>{(T)o[7], (T)o[8], (T)o[9]}, V3<T>{(T)o[10], (T)o[11], (T)o[12]}, perr, V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], e);
+    error_state9<T>(obs_rpy<T>(o), obs_vel<T>(o), perr, V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], e);
     for (int k = 0; k < M; ++k) se[threadIdx.x][k] = e[k];
   }
   __syncthreads();
@@ -285,11 +267,10 @@ __global__ __launch_bounds__(kFedceBlock) void k_dlqr_omega_compute(const Consts
     if (act_out) {
       const S* o = obs + i * kObsDim;
       const T q[4] = {(T)o[3], (T)o[4], (T)o[5], (T)o[6]};
-      const V3<T> cur = mulT(quat_to_rot(q), V3<T>{(T)o[13], (T)o[14], (T)o[15]});
-      LowLevelState<T> L;
-      ll_load<T>(ll, ld, i, L);
+      const V3<T> cur = mulT(quat_to_rot(q), obs_ang_vel<T>(o));
+      LowLevelState<T> L = load_lowlevel(ll, ld, i);
       thrust_omega_control(c, ctrl_dt, u, cur, L, act);
-      ll_store<T>(ll, ld, i, L);
+      store_lowlevel(ll, ld, i, L);
       store4<S, T>(act_out + i * 4, act);
     }
     if (u_out) {
@@ -322,8 +303,7 @@ __global__ __launch_bounds__(kFedceBlock) void k_cbf_nominal_dlqr_omega(const Co
   if (valid) {
     State<T> s;
     load_state<S, T>(state, ld, i, s);
-    P = {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)], lem[lidx(5, i, ld)],
-         lem[lidx(6, i, ld)]};
+    P = load_lemniscate(lem, ld, i);
     des = lemniscate_local(P, t);
     T e[M];
     error_state9<T>(euler_from_quat(s.q), s.v, s.p - des.p, des.v, des.yaw, e);

@@ -138,8 +138,80 @@ template <typename S, typename T> __device__ __forceinline__ void store_state(S*
   stp<S, T>(st + 12 * ld, i, s.w.z);
 }
 
+// The pieces of one control step of drone i, each stated once.  The index keeps its type from the call site (I: int, unsigned or size_t --
+// the address arithmetic is the caller's own) and the plane pointers carry no qualifier of their own beyond the kernel argument's.
+template <typename T, typename I> __device__ __forceinline__ V3<T> load_origin(const T* origin, size_t ld, I i) {
+  return {origin[i], origin[ld + i], origin[2 * ld + i]};
+}
+// the low level's PID memory: six planes (last_omega3 | integral3)
+template <typename T, typename I> __device__ __forceinline__ LowLevelState<T> load_lowlevel(const T* ll, size_t ld, I i) {
+  LowLevelState<T> L;
+  L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
+  L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
+  return L;
+}
+template <typename T, typename I> __device__ __forceinline__ void store_lowlevel(T* ll, size_t ld, I i, const LowLevelState<T>& L) {
+  ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
+  ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
+}
+// the previous step's clipped RPM: read by the drag term only; written where the drag term will read it or the handle tracks it
+// (last_rpm != NULL: include/mds.h, mds_config.track_last_rpm)
+template <bool DRAG, typename T, typename I> __device__ __forceinline__ void load_prev_rpm(const T* last_rpm, size_t ld, I i, T prev[4]) {
+  if (DRAG)
+    for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+}
+template <bool DRAG, typename T, typename I> __device__ __forceinline__ void store_last_rpm(T* last_rpm, size_t ld, I i, const T rpm[4]) {
+  if (DRAG || last_rpm)
+    for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = rpm[k];
+}
+// Lemniscate parameters of drone i, plane by plane (load_geo_in reads the same planes in 16- and 8-byte groups beside the state)
+template <typename T, typename I> __device__ __forceinline__ LemniscateParams<T> load_lemniscate(const T* lem, size_t ld, I i) {
+  return {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)], lem[lidx(5, i, ld)],
+          lem[lidx(6, i, ld)]};
+}
+// The desired state of a drone at time t in its local frame: from its Lemniscate parameters (traj_mode 1: mds_set_lemniscate made the
+// origin the trajectory centre) or from its segment table.  A rollout reads the one its mode uses once, before its loop (load_traj),
+// and samples it every step (sample_traj); a kernel that takes one step reads and samples in one branch (desired_of).
+template <typename T, typename I>
+__device__ __forceinline__ void load_traj(const int traj_mode, const T* lem, const int* tinfo, size_t ld, I i, LemniscateParams<T>& P, TrajInfo& ti) {
+  if (traj_mode == 1) P = load_lemniscate(lem, ld, i);
+  else ti = traj_info(tinfo, i);
+}
+template <typename T>
+__device__ __forceinline__ Desired<T> sample_traj(const int traj_mode, const LemniscateParams<T>& P, const SegTable& segs, const TrajInfo& ti,
+                                                  const double t, const V3<T>& org) {
+  return traj_mode == 1 ? lemniscate_local(P, t) : TrajLocal<T>::eval(segs, ti, t, org);
+}
+template <typename T, typename I>
+__device__ __forceinline__ Desired<T> desired_of(const int traj_mode, const T* lem, const SegTable& segs, const int* tinfo, size_t ld, I i,
+                                                 const double t, const V3<T>& org) {
+  if (traj_mode == 1) return lemniscate_local(load_lemniscate(lem, ld, i), t);
+  return TrajLocal<T>::eval(segs, traj_info(tinfo, i), t, org);
+}
+// the controller arm, state + desired state -> unclipped action.  CTRL 0: GeometricControl; 1: the 12-state LQRController (Kp: its Lqr12Gain)
+template <typename T, int CTRL>
+__device__ __forceinline__ void control_action(const Consts<T>& c, const void* Kp, const State<T>& s, const Desired<T>& des, T act[4]) {
+  T u[4];
+  if (CTRL == 0) {
+    const M3<T> R = quat_to_rot(s.q);
+    geometric_control<T>(c, s.p - des.p, R, s.v, mul(R, s.w), des, u, nullptr);
+  } else {
+    lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(s.q), quat_rotate(s.q, s.w), s.v, s.p - des.p, des.v, des.yaw,
+                     des.yaw_rate, u);
+  }
+  input_to_action(c, u, act);
+}
+// columns of an observation row [20]: pos 0:3 | quat 3:7 | rpy 7:10 | vel 10:13 | ang_vel 13:16 (world frame) | clipped rpm 16:20
+template <typename T, typename S> __device__ __forceinline__ V3<T> obs_pos(const S* o) { return {(T)o[0], (T)o[1], (T)o[2]}; }
+template <typename T, typename S> __device__ __forceinline__ V3<T> obs_rpy(const S* o) { return {(T)o[7], (T)o[8], (T)o[9]}; }
+template <typename T, typename S> __device__ __forceinline__ V3<T> obs_vel(const S* o) { return {(T)o[10], (T)o[11], (T)o[12]}; }
+template <typename T, typename S> __device__ __forceinline__ V3<T> obs_ang_vel(const S* o) { return {(T)o[13], (T)o[14], (T)o[15]}; }
+template <typename T, typename S> __device__ __forceinline__ void obs_rpm(const S* o, T rpm[4]) {
+  for (int k = 0; k < 4; ++k) rpm[k] = (T)o[16 + k];
+}
+
 // the state as the next kernel will load it: every component through the storage type (a no-op unless S is narrower than T)
-template <typename T, typename S> __device__ __forceinline__ State<T> state_as_stored(const State<T>& s) {
+template <typename T, typename S> __device__ __forceinline__ State<T> state_through_storage(const State<T>& s) {
   State<T> o;
   o.p = {(T)(S)s.p.x, (T)(S)s.p.y, (T)(S)s.p.z};
   for (int k = 0; k < 4; ++k) o.q[k] = (T)(S)s.q[k];
@@ -335,6 +407,8 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && !COMP) ? kStepMi
     if (COMP) load_resid<S, T>(state_lo, ld, i, r);
     T act[4], prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4];
     load4<S, T>(action + (size_t)i * 4, act);
+    // (the RPM planes are read and written in place here, not through load_prev_rpm / store_last_rpm: with the helpers this kernel's
+    // instructions come out in another order, and its assembly is pinned)
     if (DRAG)
       for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
     aviary_step_any<T, RK4, DRAG, COMP>(c, s, r, act, prev, clipped);
@@ -343,7 +417,7 @@ __global__ __launch_bounds__(kBlock, (sizeof(T) == 4 && !RK4 && !COMP) ? kStepMi
     if (DRAG || last_rpm)
       for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
     if (HAS_OBS) {
-      const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+      const V3<T> org = load_origin(origin, ld, i);
       pack_obs(s, org, clipped, o);
     }
   }
@@ -370,7 +444,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_step(const Consts<T> c, cons
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
   if (valid) {
     load_state<S, T>(state, ld, i, s);
-    org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+    org = load_origin(origin, ld, i);
     if (DRAG)
       for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
   }
@@ -390,7 +464,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_step(const Consts<T> c, cons
   if (valid) {
     store_state<S, T>(state, ld, i, s);
     if (state_lo) store_resid<S, T>(state_lo, ld, i, r);
-    if ((DRAG || last_rpm) && n_steps > 0)
+    if ((DRAG || last_rpm) && n_steps > 0)          // (in place, as in k_step: this kernel's assembly is pinned)
       for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
   }
 }
@@ -442,7 +516,7 @@ __global__ __launch_bounds__(kBlock) void k_step_env(const Consts<T> c, const En
   if (valid) {
     State<T> s;
     load_state<S, T>(state_in, ld, i, s);
-    const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+    const V3<T> org = load_origin(origin, ld, i);
     T act[4], clipped[4], prev[4] = {T(0), T(0), T(0), T(0)};
     load4<S, T>(action + (size_t)i * 4, act);
     for (int k = 0; k < 4; ++k) clipped[k] = m_clamp(act[k], T(0), c.max_rpm);
@@ -450,8 +524,7 @@ __global__ __launch_bounds__(kBlock) void k_step_env(const Consts<T> c, const En
       for (int k = 0; k < 4; ++k) prev[k] = drag_from_action ? clipped[k] : last_rpm[k * ld + i];
     env_substep<T, S, DRAG>(c, fx, D, ld, i, state_in, origin, org, s, clipped, prev);
     store_state<S, T>(state_out, ld, i, s);
-    if (store_rpm && (DRAG || last_rpm))
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+    if (store_rpm) store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
     if (obs) pack_obs(s, org, clipped, o);
   }
   if (obs) write_obs_rows<S, T>(lds, obs, n, i, valid, o);
@@ -478,33 +551,15 @@ __global__ __launch_bounds__(kBlock) void k_step_ctrl_env(const Consts<T> c, con
   if (valid) {
     State<T> s;
     load_state<S, T>(state_in, ld, i, s);
-    const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+    const V3<T> org = load_origin(origin, ld, i);
     T act[4], clipped[4], prev[4] = {T(0), T(0), T(0), T(0)};
     if (CTRL <= 1) {
-      Desired<T> des;
-      if (traj_mode == 1) {
-        const LemniscateParams<T> P = {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)],
-                                       lem[lidx(5, i, ld)], lem[lidx(6, i, ld)]};
-        des = lemniscate_local(P, t);               // local frame: mds_set_lemniscate made the origin the trajectory centre
-      } else {
-        des = TrajLocal<T>::eval(segs, traj_info(tinfo, i), t, org);
-      }
-      T u[4];
-      if (CTRL == 0) {
-        const M3<T> R = quat_to_rot(s.q);
-        geometric_control<T>(c, s.p - des.p, R, s.v, mul(R, s.w), des, u, nullptr);
-      } else {
-        lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(s.q), quat_rotate(s.q, s.w), s.v, s.p - des.p, des.v,
-                         des.yaw, des.yaw_rate, u);
-      }
-      input_to_action(c, u, act);
+      control_action<T, CTRL>(c, Kp, s, desired_of(traj_mode, lem, segs, tinfo, ld, i, t, org), act);
     } else {
       T u[4];
       load4<S, T>(u_in + (size_t)i * 4, u);
       u[0] += thrust_offset;
-      LowLevelState<T> L;
-      L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-      L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
+      LowLevelState<T> L = load_lowlevel(ll, ld, i);
       if (CTRL == 3) {   // obs still holds the previous step's row here (read and later rewritten by the same wave)
         T rpm_prev[4];
         load4<S, T>(obs + (size_t)i * kObsDim + 16, rpm_prev);
@@ -512,16 +567,13 @@ __global__ __launch_bounds__(kBlock) void k_step_ctrl_env(const Consts<T> c, con
       } else {
         thrust_omega_control(c, ctrl_dt, u, s.w, L, act);
       }
-      ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-      ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
+      store_lowlevel(ll, ld, i, L);
     }
     for (int k = 0; k < 4; ++k) clipped[k] = m_clamp(act[k], T(0), c.max_rpm);
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+    load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
     env_substep<T, S, DRAG>(c, fx, D, ld, i, state_in, origin, org, s, clipped, prev);
     store_state<S, T>(state_out, ld, i, s);
-    if (store_rpm && (DRAG || last_rpm))
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+    if (store_rpm) store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
     if (act_buf) store4<S, T>(act_buf + (size_t)i * 4, act);
     if (action_out) store4<S, T>(action_out + (size_t)i * 4, act);
     if (obs && store_rpm) pack_obs(s, org, clipped, o);
@@ -568,8 +620,7 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
     State<T>& s = in.s;
     const LemniscateParams<T>& P = in.P;
     T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4], act[4];
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+    load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
     {
       const Desired<T> des = lemniscate_local<T, Y0>(P, t);
       const Frame<T> F = make_frame(s.q, s.w);
@@ -579,8 +630,7 @@ __device__ __forceinline__ void geo_process(const Consts<T>& c, const int n, con
       if (COMP) aviary_step_comp<T, RK4, DRAG>(c, s, in.r, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, s, F, act, prev, clipped);
     }
-    if (DRAG || last_rpm)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
     if (HAS_ACT) store4<S, T>(action_out + (size_t)i * 4, act);
     if (HAS_OBS) pack_obs(s, V3<T>{P.cx, P.cy, P.cz}, clipped, o);
   }
@@ -650,21 +700,13 @@ __global__ __launch_bounds__(kBlock) void k_step_traj(const Consts<T> c, const i
   if (valid) {
     load_state<S, T>(state, ld, i, s);
     if (COMP) load_resid<S, T>(state_lo, ld, i, r);
-    const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+    const V3<T> org = load_origin(origin, ld, i);
     const Desired<T> des = TrajLocal<T>::eval(segs, traj_info(tinfo, i), t, org);
     T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4], act[4];
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    {
-      const M3<T> R = quat_to_rot(s.q);
-      const V3<T> ang_v = mul(R, s.w);
-      T u[4];
-      geometric_control<T>(c, s.p - des.p, R, s.v, ang_v, des, u, nullptr);
-      input_to_action(c, u, act);
-    }
+    load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
+    control_action<T, 0>(c, nullptr, s, des, act);
     aviary_step_any<T, RK4, DRAG, COMP>(c, s, r, act, prev, clipped);
-    if (DRAG || last_rpm)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
     if (action_out) store4<S, T>(action_out + (size_t)i * 4, act);
     if (obs) pack_obs(s, org, clipped, o);
   }
@@ -693,24 +735,14 @@ __global__ __launch_bounds__(kBlock) void k_step_lqr(const Consts<T> c, const Lq
   if (valid) {
     load_state<S, T>(state, ld, i, s);
     if (state_lo) load_resid<S, T>(state_lo, ld, i, r);
-    const V3<T> org = {origin[i], origin[ld + i], origin[2 * ld + i]};
-    Desired<T> des;
-    if (traj_mode == 1) {
-      GeoIn<T> in;
-      load_geo_in<T, S>(state, lem, ld, i, in);
-      des = lemniscate_local(in.P, t);
-    } else {
-      des = TrajLocal<T>::eval(segs, traj_info(tinfo, i), t, org);
-    }
-    T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4], act[4], u[4];
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    lqr12_control<T>(c, K, euler_from_quat(s.q), quat_rotate(s.q, s.w), s.v, s.p - des.p, des.v, des.yaw, des.yaw_rate, u);
-    input_to_action(c, u, act);
+    const V3<T> org = load_origin(origin, ld, i);
+    const Desired<T> des = desired_of(traj_mode, lem, segs, tinfo, ld, i, t, org);
+    T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4], act[4];
+    load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
+    control_action<T, 1>(c, &K, s, des, act);
     if (state_lo) aviary_step_comp<T, RK4, DRAG>(c, s, r, act, prev, clipped);
     else aviary_step<T, RK4, DRAG>(c, s, act, prev, clipped);
-    if (DRAG || last_rpm)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
     if (action_out) store4<S, T>(action_out + (size_t)i * 4, act);
     if (obs) pack_obs(s, org, clipped, o);
   }
@@ -731,8 +763,7 @@ __global__ void k_lqr12_compute(const Consts<T> c, const Lqr12Gain<T> K, const i
   const S* d = des + (size_t)i * 11;
   T u[4], act[4];
   const V3<T> perr = {(T)o[0] - (T)d[0], (T)o[1] - (T)d[1], (T)o[2] - (T)d[2]};
-  lqr12_control<T>(c, K, V3<T>{(T)o[7], (T)o[8], (T)o[9]}, V3<T>{(T)o[13], (T)o[14], (T)o[15]}, V3<T>{(T)o[10], (T)o[11], (T)o[12]}, perr,
-                   V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], (T)d[10], u);
+  lqr12_control<T>(c, K, obs_rpy<T>(o), obs_ang_vel<T>(o), obs_vel<T>(o), perr, V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], (T)d[10], u);
   input_to_action(c, u, act);
   if (u_out) store4<S, T>(u_out + (size_t)i * 4, u);
   if (act_out) store4<S, T>(act_out + (size_t)i * 4, act);
@@ -806,11 +837,10 @@ __device__ __forceinline__ void rollout_geometric_body(
   LowLevelState<T> L;
   L.last_omega = L.integral = {T(0), T(0), T(0)};
   load_geo_in<T, S>(state, lem, ld, il, in);
-  if (DRAG)
+  if (DRAG)                                        // (in place, as in k_step: this loop's assembly is pinned)
     for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + il];
   if (CTRL >= 2) {
-    L.last_omega = {ll[0 * ld + il], ll[1 * ld + il], ll[2 * ld + il]};
-    L.integral = {ll[3 * ld + il], ll[4 * ld + il], ll[5 * ld + il]};
+    L = load_lowlevel(ll, ld, il);
     if (CTRL == 3) load4<S, T>(obs_prev + il * kObsDim + 16, thr);      // calc_z_thrust(obs) of the first step
   }
   // CTRL 0: the frame of the state is carried across the step loop -- the one formed for step k's observation row (the state after
@@ -893,10 +923,7 @@ __device__ __forceinline__ void rollout_geometric_body(
     if (comp) store_resid<S, T>(state_lo, ld, i, in.r);
     if (DRAG && n_steps <= 0)
       for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = prev[k];
-    if (CTRL >= 2) {
-      ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-      ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
-    }
+    if (CTRL >= 2) store_lowlevel(ll, ld, i, L);
   }
 }
 template <typename T, typename S, bool RK4, bool DRAG, int CTRL = 0, int COMP = -1, int OBS = -1>
@@ -942,10 +969,9 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
   T prev[4] = {T(0), T(0), T(0), T(0)};        // DRAG: the previous step's clipped RPM
   if (valid) {
     load_state<S, T>(state, ld, i, s);
-    org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+    org = load_origin(origin, ld, i);
     ti = traj_info(tinfo, i);
-    if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+    load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
   }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
@@ -953,15 +979,8 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
     const bool want = omode != kObsLast || (obs_last != nullptr && last);
     if (valid) {
       const Desired<T> des = TrajLocal<T>::eval(segs, ti, t, org);
-      T u[4], act[4], clipped[4];
-      if (CTRL == 0) {
-        const M3<T> R = quat_to_rot(s.q);
-        geometric_control<T>(c, s.p - des.p, R, s.v, mul(R, s.w), des, u, nullptr);
-      } else {
-        lqr12_control<T>(c, *static_cast<const Lqr12Gain<T>*>(Kp), euler_from_quat(s.q), quat_rotate(s.q, s.w), s.v, s.p - des.p, des.v, des.yaw,
-                         des.yaw_rate, u);
-      }
-      input_to_action(c, u, act);
+      T act[4], clipped[4];
+      control_action<T, CTRL>(c, Kp, s, des, act);
       if (comp) aviary_step_comp<T, RK4, DRAG>(c, s, r, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, s, act, prev, clipped);
       if (want) pack_obs(s, org, clipped, o);
@@ -979,8 +998,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
   if (valid) {
     store_state<S, T>(state, ld, i, s);
     if (comp) store_resid<S, T>(state_lo, ld, i, r);
-    if (DRAG && n_steps <= 0)
-      for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = prev[k];
+    if (DRAG && n_steps <= 0) store_last_rpm<DRAG>(last_rpm, ld, i, prev);
   }
 }
 
@@ -988,7 +1006,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_traj(const Consts<T> c, cons
 // CBF-filtered control step (simulations/CBFTest.py:303-350) = three launches:
 //   nominal          per drone : (k_lowlevel_step in its `only` mode, or the tail of the previous step's launch) trajs[j](t), GeometricControl.compute(return_omegas) ->
 //                                u_hat = (force - M G, w_des), xdes = [0,0,yaw, vel, pos]   (:339-343)
-//   k_cbf_filter_o2* per env   : DroneQPTracker.compute_control                             (:345)
+//   k_cbf_filter_gi  per env   : DroneQPTracker.compute_control                             (:345)
 //   k_lowlevel_step  per drone : u_safe[0] += M G (:346), ThrustOmegaController (:348),
 //                                env.step(action) (:350)
 // ------------------------------------------------------------------------------------
@@ -1051,8 +1069,8 @@ __global__ void k_lqr_omega_compute(const Consts<T> c, const LqrGain<T> K, const
   const S* o = obs + (size_t)i * 20;
   const S* d = des + (size_t)i * 11;
   T u[4];
-  lqr_omega_control<T>(c, K, V3<T>{(T)o[7], (T)o[8], (T)o[9]}, V3<T>{(T)o[10], (T)o[11], (T)o[12]}, V3<T>{(T)o[0], (T)o[1], (T)o[2]},
-                       V3<T>{(T)d[0], (T)d[1], (T)d[2]}, V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], u);
+  lqr_omega_control<T>(c, K, obs_rpy<T>(o), obs_vel<T>(o), obs_pos<T>(o), V3<T>{(T)d[0], (T)d[1], (T)d[2]}, V3<T>{(T)d[3], (T)d[4], (T)d[5]},
+                       (T)d[9], u);
   store4<S, T>(u_out + (size_t)i * 4, u);
 }
 
@@ -1090,11 +1108,10 @@ __global__ void k_lqr_yank_omega_compute(const Consts<T> c, const LqrYoGain<T> K
   if (i >= n) return;
   const S* o = obs + (size_t)i * 20;
   const S* d = des + (size_t)i * 11;
-  const T rpm[4] = {(T)o[16], (T)o[17], (T)o[18], (T)o[19]};
-  T u[4];
-  lqr_yank_omega_control<T>(c, K, V3<T>{(T)o[7], (T)o[8], (T)o[9]}, rpm, V3<T>{(T)o[10], (T)o[11], (T)o[12]},
-                            V3<T>{(T)o[0], (T)o[1], (T)o[2]}, V3<T>{(T)d[0], (T)d[1], (T)d[2]}, V3<T>{(T)d[3], (T)d[4], (T)d[5]},
-                            (T)d[9], u);
+  T rpm[4], u[4];
+  obs_rpm(o, rpm);
+  lqr_yank_omega_control<T>(c, K, obs_rpy<T>(o), rpm, obs_vel<T>(o), obs_pos<T>(o), V3<T>{(T)d[0], (T)d[1], (T)d[2]},
+                            V3<T>{(T)d[3], (T)d[4], (T)d[5]}, (T)d[9], u);
   store4<S, T>(u_out + (size_t)i * 4, u);
 }
 
@@ -1119,9 +1136,7 @@ __global__ __launch_bounds__(kBlock) void k_lowlevel_step(const Consts<T> c, con
       T u[4];
       load4<S, T>(u_in + (size_t)i * 4, u);
       u[0] += thrust_offset;
-      LowLevelState<T> L;
-      L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-      L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
+      LowLevelState<T> L = load_lowlevel(ll, ld, i);
       T act[4], prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4];
       // compute_low_level rotates obs[13:16] (= R w) back with R^T: the body rate is the state's w
       if (YANK) {   // obs still holds the previous step's row here: every row is read and later rewritten by the same wave
@@ -1131,15 +1146,12 @@ __global__ __launch_bounds__(kBlock) void k_lowlevel_step(const Consts<T> c, con
       } else {
         thrust_omega_control(c, ctrl_dt, u, s.w, L, act);
       }
-      ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-      ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
-      if (DRAG)
-        for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+      store_lowlevel(ll, ld, i, L);
+      load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
       aviary_step_any<T, RK4, DRAG, COMP>(c, s, r, act, prev, clipped);
-      if (DRAG || last_rpm)
-        for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+      store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
       if (action_out) store4<S, T>(action_out + (size_t)i * 4, act);
-      pack_obs(s, V3<T>{origin[i], origin[ld + i], origin[2 * ld + i]}, clipped, o);
+      pack_obs(s, load_origin(origin, ld, i), clipped, o);
     }
   }
   if (do_step) write_obs_rows<S, T>(lds, obs, n, i, valid, o);
@@ -1149,7 +1161,7 @@ __global__ __launch_bounds__(kBlock) void k_lowlevel_step(const Consts<T> c, con
       if (COMP) store_resid<S, T>(state_lo, ld, i, r);
     }
     if (!YANK && nx.unom != nullptr) {        // the nominal controller on the state just stored (only: on the state just loaded)
-      const State<T> sn = state_as_stored<T, S>(s);
+      const State<T> sn = state_through_storage<T, S>(s);
       cbf_nominal_of<T, S>(&c, &nx, &sn, i, ld);
     }
   }
@@ -1171,20 +1183,17 @@ __global__ void k_thrust_omega(const Consts<T> c, const int n, const size_t ld, 
   } else {
     const S* o = obs_or_rates + (size_t)i * 20;
     const T q[4] = {(T)o[3], (T)o[4], (T)o[5], (T)o[6]};
-    cur = mulT(quat_to_rot(q), V3<T>{(T)o[13], (T)o[14], (T)o[15]});
+    cur = mulT(quat_to_rot(q), obs_ang_vel<T>(o));
   }
-  LowLevelState<T> L;
-  L.last_omega = {ll[0 * ld + i], ll[1 * ld + i], ll[2 * ld + i]};
-  L.integral = {ll[3 * ld + i], ll[4 * ld + i], ll[5 * ld + i]};
+  LowLevelState<T> L = load_lowlevel(ll, ld, i);
   if (yank) {   // YankOmegaController: needs the obs (calc_z_thrust), never combined with body_rates_given
-    const S* o = obs_or_rates + (size_t)i * 20;
-    const T rpm_prev[4] = {(T)o[16], (T)o[17], (T)o[18], (T)o[19]};
+    T rpm_prev[4];
+    obs_rpm(obs_or_rates + (size_t)i * 20, rpm_prev);
     yank_omega_control(c, ctrl_dt, u, rpm_prev, cur, L, act);
   } else {
     thrust_omega_control(c, ctrl_dt, u, cur, L, act);
   }
-  ll[0 * ld + i] = L.last_omega.x; ll[1 * ld + i] = L.last_omega.y; ll[2 * ld + i] = L.last_omega.z;
-  ll[3 * ld + i] = L.integral.x; ll[4 * ld + i] = L.integral.y; ll[5 * ld + i] = L.integral.z;
+  store_lowlevel(ll, ld, i, L);
   store4<S, T>(rpm + (size_t)i * 4, act);
 }
 
@@ -1211,7 +1220,7 @@ __global__ __launch_bounds__(kBlock) void k_dslpid(const Consts<T> c, const DslP
     if (STEP && state_lo) load_resid<S, T>(state_lo, ld, i, r);
     if (STEP || !obs_in) {      // controller only with obs_in == NULL: from the handle's own state (ground effect / downwash steps)
       load_state<S, T>(state, ld, i, s);
-      org = {origin[i], origin[ld + i], origin[2 * ld + i]};
+      org = load_origin(origin, ld, i);
     } else {
       const S* ob = obs_in + (size_t)i * 20;
       s.p = {(T)ob[0], (T)ob[1], (T)ob[2]};
@@ -1232,12 +1241,10 @@ __global__ __launch_bounds__(kBlock) void k_dslpid(const Consts<T> c, const DslP
     pid[6 * ld + i] = P.int_rpy.x; pid[7 * ld + i] = P.int_rpy.y; pid[8 * ld + i] = P.int_rpy.z;
     if (action_out) store4<S, T>(action_out + (size_t)i * 4, act);
     if (STEP) {
-      if (DRAG)
-        for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+      load_prev_rpm<DRAG>(last_rpm, ld, i, prev);
       if (state_lo) aviary_step_comp<T, RK4, DRAG>(c, s, r, act, prev, clipped);
       else aviary_step<T, RK4, DRAG>(c, s, act, prev, clipped);
-      if (DRAG || last_rpm)
-        for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = clipped[k];
+      store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
       if (obs) pack_obs(s, org, clipped, o);
     }
   }
@@ -1267,7 +1274,7 @@ __global__ __launch_bounds__(kBlock) void k_get_obs(const int n, const size_t ld
     const T kNaN = __builtin_nanf("");
     const T rpm[4] = {last_rpm ? last_rpm[i] : kNaN, last_rpm ? last_rpm[ld + i] : kNaN, last_rpm ? last_rpm[2 * ld + i] : kNaN,
                       last_rpm ? last_rpm[3 * ld + i] : kNaN};
-    pack_obs(s, V3<T>{origin[i], origin[ld + i], origin[2 * ld + i]}, rpm, o);
+    pack_obs(s, load_origin(origin, ld, i), rpm, o);
   }
   write_obs_rows<S, T>(lds, obs, n, i, valid, o);
 }
@@ -1351,8 +1358,7 @@ template <typename T, typename S>
 __global__ void k_lemniscate_eval(const int n, const size_t ld, const double t, const T* __restrict__ lem, S* __restrict__ des) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  LemniscateParams<T> P = {lem[lidx(0, i, ld)], lem[lidx(1, i, ld)], lem[lidx(2, i, ld)], lem[lidx(3, i, ld)], lem[lidx(4, i, ld)],
-                           lem[lidx(5, i, ld)], lem[lidx(6, i, ld)]};
+  const LemniscateParams<T> P = load_lemniscate(lem, ld, i);
   const Desired<T> d = lemniscate_local(P, t);
   S* o = des + (size_t)i * 11;
   o[0] = (S)(d.p.x + P.cx); o[1] = (S)(d.p.y + P.cy); o[2] = (S)(d.p.z + P.cz);
@@ -1371,7 +1377,7 @@ __global__ void k_geometric_compute(const Consts<T> c, const int n, const S* __r
   // utils/model_conversions.py:105-114 obs_to_geo_model
   const T q[4] = {(T)o[3], (T)o[4], (T)o[5], (T)o[6]};
   const M3<T> R = quat_to_rot(q);
-  const V3<T> p = {(T)o[0], (T)o[1], (T)o[2]}, v = {(T)o[10], (T)o[11], (T)o[12]}, w = {(T)o[13], (T)o[14], (T)o[15]};
+  const V3<T> p = obs_pos<T>(o), v = obs_vel<T>(o), w = obs_ang_vel<T>(o);
   Desired<T> D;
   D.p = {(T)d[0], (T)d[1], (T)d[2]};
   D.v = {(T)d[3], (T)d[4], (T)d[5]};

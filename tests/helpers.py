@@ -148,3 +148,53 @@ def full_size_or_slice(E):
     if oracle_threads() >= 8:
         return E, ""
     return max(64, E // 8), f" [only {oracle_threads()} host cores: the first {max(64, E // 8)} of {E} envs]"
+
+
+def gpu_namespace():
+    """what the GPU tests' `mds` fixture hands out, for a child process that has no fixture: the classes bound to whatever library
+    MDS_LIB_PATH names"""
+    import types
+
+    import torch
+
+    import multidronesim_amd
+    multidronesim_amd.load_library()
+    from multidronesim_amd.envs.CtrlAviary import CtrlAviary, DroneModel, Physics
+    return types.SimpleNamespace(CtrlAviary=CtrlAviary, DroneModel=DroneModel, Physics=Physics, torch=torch)
+
+
+def dump_flights(module, func, path):
+    """(the child process of parent_library_flights: MODULE.FUNC(mds) -> {name: array}, saved to path)"""
+    import importlib
+    np.savez(path, **getattr(importlib.import_module(module), func)(gpu_namespace()))
+
+
+def parent_library_flights(module, func, tmp_path):
+    """{name: array} of MODULE.FUNC flown on the libmds.so that MDS_PARENT_LIB names (built from the parent commit): a child process
+    loads it through MDS_LIB_PATH.  Skips the calling test when MDS_PARENT_LIB is not set."""
+    import os
+    import subprocess
+    import sys
+
+    import pytest
+    parent = os.environ.get("MDS_PARENT_LIB")
+    if not parent:
+        pytest.skip("MDS_PARENT_LIB is not set: no library of the parent commit to compare with")
+    assert os.path.exists(parent), parent
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = str(tmp_path / "parent.npz")
+    subprocess.check_call([sys.executable, "-c", "from tests.helpers import dump_flights; dump_flights(%r, %r, %r)" % (module, func, path)],
+                          cwd=root, env=dict(os.environ, MDS_LIB_PATH=parent), timeout=300)
+    return np.load(path)
+
+
+def assert_same_bits(ref, flights):
+    """every array of flights equals ref's of the same name bit for bit (float32 / float64 / integer arrays)"""
+    assert sorted(ref.files if hasattr(ref, "files") else ref) == sorted(flights)
+    for k, v in flights.items():
+        r = ref[k]
+        assert r.dtype == v.dtype and r.shape == v.shape, k
+        view = {4: np.uint32, 8: np.uint64}[v.dtype.itemsize]
+        differ = np.ascontiguousarray(r).view(view) != np.ascontiguousarray(v).view(view)
+        print("%s: %d values, %d differ from the parent library's" % (k, v.size, differ.sum()))
+        assert not differ.any(), k

@@ -95,18 +95,6 @@ def fly_all(mds):
     return {"%s_%dx%d_%s" % (model, E, D, k): v for model in ("CF2P", "CF2X") for E, D in SHAPES for k, v in fly(mds, model, E, D).items()}
 
 
-def dump(path):
-    """(the child process of the comparison below: the same flights on whatever library MDS_LIB_PATH names)"""
-    import types
-
-    import torch
-
-    import multidronesim_amd
-    multidronesim_amd.load_library()
-    from multidronesim_amd.envs.CtrlAviary import CtrlAviary, DroneModel, Physics
-    np.savez(path, **fly_all(types.SimpleNamespace(CtrlAviary=CtrlAviary, DroneModel=DroneModel, Physics=Physics, torch=torch)))
-
-
 @pytest.fixture(scope="module")
 def flights(mds):
     return fly_all(mds)
@@ -124,18 +112,4 @@ def test_twenty_steps_stay_finite_and_within_the_rpm_clip(flights):
 
 
 def test_rows_and_state_are_the_parent_librarys_bit_for_bit(flights, tmp_path):
-    parent = os.environ.get("MDS_PARENT_LIB")
-    if not parent:
-        pytest.skip("MDS_PARENT_LIB is not set: no library of the parent commit to compare with")
-    assert os.path.exists(parent), parent
-    path = str(tmp_path / "parent.npz")
-    env = dict(os.environ, MDS_LIB_PATH=parent)
-    subprocess.check_call([sys.executable, "-c", "from tests.test_gpu_step_clamps import dump; dump(%r)" % path], cwd=ROOT, env=env, timeout=300)
-    ref = np.load(path)
-    assert sorted(ref.files) == sorted(flights)
-    for k, v in flights.items():
-        r = ref[k]
-        assert r.dtype == v.dtype and r.shape == v.shape, k
-        differ = r.view(np.uint32) != v.view(np.uint32)
-        print("%s: %d values, %d differ from the parent library's" % (k, v.size, differ.sum()))
-        assert not differ.any(), k
+    H.assert_same_bits(H.parent_library_flights("tests.test_gpu_step_clamps", "fly_all", tmp_path), flights)
