@@ -238,6 +238,50 @@ int mds_rollout_step_fused(mds_handle* h, const void* actions_dev, int n_action_
 /* mds_reset's effect again from the poses it was last given, enqueued on `stream` without any host copy or synchronisation */
 int mds_reset_async(mds_handle* h, void* stream);
 
+/* PER-ENV EPISODES, decided and restarted on the device inside the rollout kernel (the rule: multidronesim_amd/csrc/mds_episode.hpp).
+ * After every control step each drone is tested on its stepped state, in the handle's compute type:
+ *   cause bit 0  a state component is not finite (always on)
+ *             1  world z < z_min or > z_max
+ *             2  |p - home| > max_dist, home = the drone's reset position as mds_reset stores it
+ *             3  the body z axis is more than max_tilt (rad, in (0, pi)) off world z: 1 - 2 (qx^2 + qy^2) < cos(max_tilt)
+ *             4  |v| > max_speed            5  |body rates| > max_rate
+ * A threshold that is not finite or out of range (max_dist / max_speed / max_rate <= 0, max_tilt outside (0, pi)) switches its test
+ * off.  An env is terminated when a drone of it has a cause bit, truncated when it is not terminated and its episode has run
+ * max_steps control steps (0: never), done when either; a done env has ALL its drones put back: state bit-identical to
+ * mds_reset_async, zero RPM echo.  Reward of the transition, per env: sum over its drones, in drone order, of
+ * max(0, reward_r0 - |p - target|^4), less term_penalty when terminated ([UPSTREAM] HoverAviary._computeReward's form). */
+typedef struct mds_episode_params {
+  int32_t max_steps;
+  int32_t reserved;
+  double z_min, z_max, max_dist, max_tilt, max_speed, max_rate;
+  double reward_r0, term_penalty;
+} mds_episode_params;
+/* every test off (infinite thresholds), max_steps 0, reward_r0 2, term_penalty 0 */
+int mds_default_episode_params(mds_episode_params* params);
+/* Configures (params NULL: switches off) the episodes of the handle: builds the reset image from the poses of the last mds_reset
+ * (MDS_ESTATE without one), takes the targets (target_host double [n,3], world frame; NULL: every drone's reset position) and
+ * zeroes the counters.  A later mds_reset rebuilds the image and restarts every env's running episode (mds_reset_async restarts
+ * them too); a change of the local-frame origin rebuilds it as well.  MDS_EUNSUPPORTED for MDS_F32C handles, the ground-effect /
+ * downwash physics modes and more than 128 drones per env.  No other entry point changes its behaviour on a configured handle. */
+int mds_set_episodes(mds_handle* h, const mds_episode_params* params, const double* target_host, void* stream);
+/* mds_rollout_step_fused's loop with episodes: step j = first_step + k applies actions_dev[j % n_action_sets], and writes into slot
+ * j % log_slots of each ring that is not NULL: obs_log_dev [log_slots, n, 20] the observation the step produced (the transition's
+ * result, BEFORE any reset), reward_log_dev [log_slots, E] (compute type: float, double for MDS_F64) and flags_log_dev
+ * [log_slots, E] (bit 0 terminated, bit 1 truncated, bits 8..13 the OR of the drones' cause bits).  steps_per_launch control steps
+ * run per kernel launch with the state in registers.  obs_dev (or NULL) receives the observation after the call's last step: the
+ * CURRENT one, post-reset rows where an env was done.  Alignment as for mds_rollout_step (MDS_EALIGN); MDS_ESTATE without
+ * mds_set_episodes.  Only enqueues, on the caller's stream. */
+int mds_rollout_episodes(mds_handle* h, const void* actions_dev, int n_action_sets, int first_step, int n_steps, void* obs_log_dev,
+                         int log_slots, void* reward_log_dev, int32_t* flags_log_dev, int steps_per_launch, void* obs_dev, void* stream);
+/* The policy-in-the-loop form, one control step: obs_dev [n,20] is what the policy acts on next (post-reset rows where done),
+ * final_obs_dev (or NULL) the transition's rows, reward_dev [E], flags_dev [E] as above.  Equal to mds_rollout_episodes with one step. */
+int mds_step_episodes(mds_handle* h, const void* action_dev, void* obs_dev, void* final_obs_dev, void* reward_dev, int32_t* flags_dev,
+                      void* stream);
+/* Device pointers to the per-env counters, [E] each: ptrs[0] length (int32) and ptrs[1] ret (compute type) of the running episode;
+ * of the completed episodes ptrs[2] count (int32), ptrs[3] sum_return (compute type), ptrs[4] sum_length (int32).  Per env, no
+ * atomics: the caller reduces.  Valid until mds_destroy. */
+int mds_episode_ptrs(mds_handle* h, void* ptrs[5]);
+
 /* How mds_rollout_geometric / mds_rollout_step / mds_rollout_cbf_geometric issue their steps.  Drones never read each
  * other's rows in the fused step (and a barrier row couples drones of one env only), so the two halves of the shard are
  * independent step chains: on two internal streams one half's load/store bursts fill the other's compute phase, and the

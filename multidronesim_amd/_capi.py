@@ -41,6 +41,11 @@ class MdsDslPidGains(C.Structure):
     _fields_ = [(k, C.c_double * 3) for k in ("P_COEFF_FOR", "I_COEFF_FOR", "D_COEFF_FOR", "P_COEFF_TOR", "I_COEFF_TOR", "D_COEFF_TOR")]
 
 
+class MdsEpisodeParams(C.Structure):
+    _fields_ = [("max_steps", C.c_int32), ("reserved", C.c_int32)] + [(k, C.c_double) for k in (
+        "z_min", "z_max", "max_dist", "max_tilt", "max_speed", "max_rate", "reward_r0", "term_penalty")]
+
+
 class MdsError(RuntimeError):
     def __init__(self, status, where, detail):
         super().__init__(f"{where}: {detail} (mds_status {status})")
@@ -85,6 +90,11 @@ PROTOTYPES = {
     "mds_rollout_step": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     "mds_rollout_step_fused": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "mds_reset_async": (C.c_int, [_P, _P]),
+    "mds_default_episode_params": (C.c_int, [C.POINTER(MdsEpisodeParams)]),
+    "mds_set_episodes": (C.c_int, [_P, C.POINTER(MdsEpisodeParams), _PD, _P]),
+    "mds_rollout_episodes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "mds_step_episodes": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "mds_episode_ptrs": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "mds_rollout_geometric_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
     "mds_lemniscate_eval": (C.c_int, [_P, C.c_double, _P, _P]),
     "mds_geometric_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),
@@ -152,6 +162,12 @@ PROTOTYPES = {
 _lib = None
 
 
+def _not_exported(name, lib_path):
+    def call(*args):
+        raise MdsError(-6, name, f"{lib_path} (selected with MDS_LIB_PATH) does not export this entry point")
+    return call
+
+
 def load_library(path: str | None = None):
     """dlopen libmds.so and bind every prototype.  Raises (never falls back) when the
     library has not been built -- run ``python -c 'import __graft_entry__ as g; g.build()'``."""
@@ -166,8 +182,17 @@ def load_library(path: str | None = None):
     except Exception:  # pragma: no cover - torch is only needed for device tensors
         pass
     lib = C.CDLL(p)
+    other_build = path is None and bool(os.environ.get("MDS_LIB_PATH"))
     for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+        try:
+            fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+        except AttributeError:
+            # another build chosen with MDS_LIB_PATH (an older commit's, say) may predate an entry point: it loads, and the entry point it
+            # lacks raises when called.  The package's own libmds.so must export everything.
+            if not other_build:
+                raise
+            setattr(lib, name, _not_exported(name, p))
+            continue
         fn.restype = res
         fn.argtypes = args
     if path is None:

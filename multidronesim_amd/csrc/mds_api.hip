@@ -18,6 +18,9 @@
 #ifndef MDS_PART
 #define MDS_PART 3
 #endif
+#if MDS_PART & 1
+#include "mds_episode_kernels.hip"  // per-env episodes inside the rollout kernel (part 1 only)
+#endif
 #if MDS_PART & 2
 #include "mds_cbf_kernels.hip"      // (part 2 only: it defines a non-template kernel)
 #include "mds_fedce_kernels.hip"    // FedCE identification and the dLQR kernels (part 2 only)
@@ -187,6 +190,14 @@ struct mds_handle {
   double* care_K64[2] = {nullptr, nullptr};      // [E, 4D, MD] float64 staging when the caller passes no K_dev
   bool track_rpm = false;        // last_rpm planes maintained by every step kernel (DYN_DRAG, order-3 CBF, or cfg.track_last_rpm)
   bool rpm_stale = false;        // a step ran without tracking since the last reset
+  // per-env episodes (mds_set_episodes): the rule, the reset image k_reset wrote (layout and dtype of `state`), the targets and the counters
+  bool ep_on = false;
+  mds_episode_params ep = {};
+  void* ep_image = nullptr;            // S [13][ld]
+  void* ep_target = nullptr;           // T [4][ld]: three planes of local-frame targets (the fourth: k_reset's RPM planes while the image is built)
+  double* ep_target_world = nullptr;   // double [n,3]: the caller's targets; NULL: the reset positions
+  void* ep_counters = nullptr;         // five arrays of 8-byte slots, [ep_slots] each: length | ret | count | sum_return | sum_length
+  size_t ep_slots = 0;
 };
 
 template <typename T> static inline const HostParams<T>& params(const mds_handle* h) {
@@ -590,6 +601,10 @@ int mds_destroy(mds_handle* h) {
   if (h->lem) (void)hipFree(h->lem);
   if (h->scratch) (void)hipFree(h->scratch);
   if (h->init_pose) (void)hipFree(h->init_pose);
+  if (h->ep_image) (void)hipFree(h->ep_image);
+  if (h->ep_target) (void)hipFree(h->ep_target);
+  if (h->ep_target_world) (void)hipFree(h->ep_target_world);
+  if (h->ep_counters) (void)hipFree(h->ep_counters);
   if (h->pair_ij) (void)hipFree(h->pair_ij);
   if (h->obstacles) (void)hipFree(h->obstacles);
   if (h->cbf_order) (void)hipFree(h->cbf_order);
@@ -651,6 +666,28 @@ static int launch_reset_range(mds_handle* h, hipStream_t st, size_t i0, size_t i
   return MDS_OK;
 }
 
+// Per-env episodes, set-up side: the reset image is what mds_reset_async would write -- k_reset itself, into the library's second state
+// buffer -- and the local-frame targets are formed against the current origin; both are rebuilt whenever the poses (mds_reset) or the
+// origin (mds_set_origin and the trajectory uploads that call it) change.  Enqueue only.
+static int episode_build_image(mds_handle* h, hipStream_t st) {
+  const double* xyz = h->init_pose;
+  const double* rpy = h->init_pose + (size_t)3 * h->n;
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    // (k_reset also zeroes four RPM planes: the target buffer has room for them, and the targets are written after it, in stream order)
+    k_reset<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, xyz, rpy, (const T*)h->origin, (S*)h->ep_image, (T*)h->ep_target, 0, (S*)nullptr);
+    k_episode_targets<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, h->ep_target_world, (const T*)h->origin, (const S*)h->ep_image,
+                                                                   (T*)h->ep_target);
+  });
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+// the running episode of every env starts anew (length, return); the statistics of the completed ones stay
+static int episode_restart(mds_handle* h, hipStream_t st) {
+  MDS_HIP(hipMemsetAsync(h->ep_counters, 0, 2 * h->ep_slots * 8, st));
+  return MDS_OK;
+}
+
 int mds_reset(mds_handle* h, const double* xyz, const double* rpy, void* stream) {
   MDS_DEV(h);
   if (!h || !xyz || !rpy) return fail(MDS_EINVAL, "mds_reset: null argument");
@@ -663,6 +700,10 @@ int mds_reset(mds_handle* h, const double* xyz, const double* rpy, void* stream)
   MDS_HIP(hipMemsetAsync(h->ll, 0, 6 * h->ld * comp_size(h->cfg.dtype), st));
   MDS_HIP(hipMemsetAsync(h->pid, 0, 9 * h->ld * comp_size(h->cfg.dtype), st));
   h->rpm_stale = false;
+  if (h->ep_on) {                      // new poses: a new reset image, and every env's running episode starts anew
+    if (int rc = episode_build_image(h, st)) return rc;
+    if (int rc = episode_restart(h, st)) return rc;
+  }
   MDS_HIP(hipStreamSynchronize(st));   // host buffers may be reused by the caller
   return MDS_OK;
 }
@@ -676,6 +717,8 @@ int mds_reset_async(mds_handle* h, void* stream) {
   MDS_HIP(hipMemsetAsync(h->ll, 0, 6 * h->ld * comp_size(h->cfg.dtype), st));
   MDS_HIP(hipMemsetAsync(h->pid, 0, 9 * h->ld * comp_size(h->cfg.dtype), st));
   h->rpm_stale = false;
+  if (h->ep_on)
+    if (int rc = episode_restart(h, st)) return rc;
   return MDS_OK;
 }
 
@@ -730,6 +773,8 @@ int mds_set_origin(mds_handle* h, const double* origin, void* stream) {
     k_set_origin<T, S><<<grid_for(h->n, 256), 256, 0, st>>>(h->n, h->ld, h->scratch, (T*)h->origin, (S*)h->state, (S*)h->state_lo);
   });
   MDS_HIP(hipGetLastError());
+  if (h->ep_on)                        // the reset image and the targets are local-frame values
+    if (int rc = episode_build_image(h, st)) return rc;
   MDS_HIP(hipStreamSynchronize(st));
   return MDS_OK;
 }
@@ -1138,6 +1183,99 @@ int mds_rollout_step_fused(mds_handle* h, const void* actions, int n_action_sets
     }, rk4, drag);
   }
   return check_launches();
+}
+
+// ---- per-env episodes (mds_episode.hpp, mds_episode_kernels.hip) ----
+int mds_default_episode_params(mds_episode_params* p) {
+  if (!p) return fail(MDS_EINVAL, "mds_default_episode_params: null argument");
+  memset(p, 0, sizeof(*p));
+  p->z_min = -(double)INFINITY;
+  p->z_max = p->max_dist = p->max_tilt = p->max_speed = p->max_rate = (double)INFINITY;
+  p->reward_r0 = 2.0;
+  return MDS_OK;
+}
+
+int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* target_host, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_set_episodes: null handle");
+  if (!p) {
+    h->ep_on = false;
+    return MDS_OK;
+  }
+  if (p->max_steps < 0 || !(p->reward_r0 == p->reward_r0) || !(p->term_penalty == p->term_penalty))
+    return fail(MDS_EINVAL, "mds_set_episodes: max_steps < 0, or reward_r0 / term_penalty is NaN");
+  if (h->cfg.dtype == MDS_F32C || h->envfx || h->cfg.num_drones > kBlock / 2)
+    return fail(MDS_EUNSUPPORTED, "mds_set_episodes: built for MDS_F32 / MDS_F64 / MDS_F16 storage, DYN / DYN_DRAG physics and at most 128 drones per env");
+  if (!h->init_pose) return fail(MDS_ESTATE, "mds_set_episodes: needs an earlier mds_reset");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t es = elem_size(h->cfg.dtype), cs = comp_size(h->cfg.dtype), tb = (size_t)h->n * 3 * sizeof(double);
+  if (!h->ep_image) MDS_HIP(hipMalloc(&h->ep_image, 13 * h->ld * es));
+  if (!h->ep_target) MDS_HIP(hipMalloc(&h->ep_target, 4 * h->ld * cs));
+  if (!h->ep_counters) {
+    h->ep_slots = ((size_t)h->cfg.num_envs + 31) / 32 * 32;
+    MDS_HIP(hipMalloc(&h->ep_counters, 5 * h->ep_slots * 8));
+  }
+  if (target_host) {
+    if (!h->ep_target_world) MDS_HIP(hipMalloc((void**)&h->ep_target_world, tb));
+    MDS_HIP(hipMemcpyAsync(h->ep_target_world, target_host, tb, hipMemcpyHostToDevice, st));
+  } else if (h->ep_target_world) {
+    MDS_HIP(hipStreamSynchronize(st));          // (set-up path: nothing enqueued may still read it)
+    (void)hipFree(h->ep_target_world);
+    h->ep_target_world = nullptr;
+  }
+  h->ep = *p;
+  if (int rc = episode_build_image(h, st)) return rc;
+  MDS_HIP(hipMemsetAsync(h->ep_counters, 0, 5 * h->ep_slots * 8, st));
+  h->ep_on = true;
+  if (target_host) MDS_HIP(hipStreamSynchronize(st));   // host buffer may be reused by the caller
+  return MDS_OK;
+}
+
+int mds_episode_ptrs(mds_handle* h, void* ptrs[5]) {
+  if (!h || !ptrs) return fail(MDS_EINVAL, "mds_episode_ptrs: null argument");
+  if (!h->ep_counters) return fail(MDS_ESTATE, "mds_episode_ptrs: no mds_set_episodes yet");
+  for (int k = 0; k < 5; ++k) ptrs[k] = (char*)h->ep_counters + (size_t)k * h->ep_slots * 8;
+  return MDS_OK;
+}
+
+int mds_rollout_episodes(mds_handle* h, const void* actions, int n_action_sets, int first_step, int n_steps, void* obs_log, int log_slots,
+                         void* reward_log, int32_t* flags_log, int steps_per_launch, void* obs, void* stream) {
+  MDS_DEV(h);
+  const bool ring = obs_log || reward_log || flags_log;
+  if (steps_per_launch < 1 || (ring && log_slots < 1)) return fail(MDS_EINVAL, "mds_rollout_episodes: arguments");
+  if (int rc = rollout_step_args(h, "mds_rollout_episodes", actions, n_action_sets, first_step, n_steps, obs_log, log_slots, 0)) return rc;
+  if (!aligned16(obs) || !aligned16(reward_log) || !aligned16(flags_log))
+    return fail(MDS_EALIGN, "mds_rollout_episodes: obs_dev/reward_log_dev/flags_log_dev");
+  if (!h->ep_on) return fail(MDS_ESTATE, "mds_rollout_episodes: no episodes configured (mds_set_episodes)");
+  hipStream_t st = (hipStream_t)stream;
+  const int D = h->cfg.num_drones, epb = episode_envs_per_block(D);
+  const dim3 grid((unsigned)((h->cfg.num_envs + epb - 1) / epb));
+  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
+  const mds_episode_params& p = h->ep;
+  for (Chunks c{n_steps, steps_per_launch, 0.0, 0.0, ring ? first_step % log_slots : 0, ring ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
+    const int ks = c.len(), a0 = (int)(((long long)first_step + c.k) % n_action_sets), s0 = c.slot;
+    const bool last = c.k + ks == n_steps;
+    with_flags([&](auto RK4, auto DRAG) {
+      with_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+        EpisodeRule<T> rule;
+        fill_episode_rule<T>(p.max_steps, p.z_min, p.z_max, p.max_dist, p.max_tilt, p.max_speed, p.max_rate, p.reward_r0, p.term_penalty, rule);
+        char* cb = (char*)h->ep_counters;
+        const size_t sl = h->ep_slots * 8;
+        const EpisodeCounters<T> cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
+        k_rollout_episodes<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(
+            params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
+            (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks,
+            (S*)(last ? obs : nullptr), cnt);
+      });
+    }, rk4, drag);
+  }
+  return check_launches();
+}
+
+int mds_step_episodes(mds_handle* h, const void* action, void* obs, void* final_obs, void* reward, int32_t* flags, void* stream) {
+  if (!h || !action) return fail(MDS_EINVAL, "mds_step_episodes: null argument");
+  return mds_rollout_episodes(h, action, 1, 0, 1, final_obs, 1, reward, flags, 1, obs, stream);
 }
 
 int mds_set_rollout_streams(mds_handle* h, int n_streams) {

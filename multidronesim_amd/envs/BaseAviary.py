@@ -408,6 +408,99 @@ class BaseAviary:
         self.step_counter += n_steps * self.PYB_STEPS_PER_CTRL
         return obs_log
 
+    # ------------------------------------------------------------------ per-env episodes on the device
+    def set_episodes(self, max_steps: int = 0, z_min=None, z_max=None, max_dist=None, max_tilt=None, max_speed=None, max_rate=None,
+                     reward_r0: float = 2.0, term_penalty: float = 0.0, target=None, enabled: bool = True):
+        """Per-env episodes decided and restarted inside the rollout kernel (mds_set_episodes).  A drone terminates its env when a
+        state component is not finite, its world z leaves [``z_min``, ``z_max``], it is more than ``max_dist`` from its reset position,
+        its body z axis is more than ``max_tilt`` rad off vertical, or it is faster than ``max_speed`` / spins faster than ``max_rate``
+        (``None``: test off); an env is truncated after ``max_steps`` control steps (0: never).  A done env has all its drones put
+        back to their initial poses.  Reward per env: sum over drones of ``max(0, reward_r0 - |p - target|^4)``, less ``term_penalty``
+        when terminated; ``target`` [E,D,3] / [D,3] world frame (default: the initial positions).  ``enabled=False`` switches it off."""
+        self._require_open()
+        if not enabled:
+            capi.check(self._lib.mds_set_episodes(self._h, None, None, self._stream()), "mds_set_episodes")
+            return
+        p = capi.MdsEpisodeParams()
+        capi.check(self._lib.mds_default_episode_params(C.byref(p)), "mds_default_episode_params")
+        p.max_steps = int(max_steps)
+        for name, val in (("z_min", z_min), ("z_max", z_max), ("max_dist", max_dist), ("max_tilt", max_tilt), ("max_speed", max_speed),
+                          ("max_rate", max_rate)):
+            if val is not None:
+                setattr(p, name, float(val))
+        p.reward_r0, p.term_penalty = float(reward_r0), float(term_penalty)
+        tgt = None
+        if target is not None:
+            tgt = np.ascontiguousarray(self._broadcast_init(target).reshape(self.n, 3))
+        capi.check(self._lib.mds_set_episodes(self._h, C.byref(p), capi.as_double_ptr(tgt) if tgt is not None else None, self._stream()),
+                   "mds_set_episodes")
+
+    def _episode_dtype(self):
+        return torch.float64 if self.dtype == torch.float64 else torch.float32
+
+    def step_episodes(self, action: torch.Tensor, final_obs: torch.Tensor | None = None):
+        """One control step with the episode rule (mds_step_episodes): ``(obs, reward[E], terminated[E], truncated[E], info)``, device
+        tensors.  ``obs`` is what a policy acts on next: the rows of a done env are its post-reset observation; ``final_obs``
+        (optional [E,D,20] tensor) receives the transition's own rows.  ``info["flags"]``: the int32 flags word per env (bit 0
+        terminated, bit 1 truncated, bits 8..13 the causes).  The returned tensors are reused by the next call."""
+        self._require_open()
+        act = to_device(action, self.device, self.dtype)
+        if act.numel() != self.n * capi.ACT_DIM or not act.is_contiguous():
+            raise ValueError(f"action must be a contiguous tensor of {self.NUM_ENVS}x{self.NUM_DRONES}x4 RPMs, got shape {tuple(act.shape)}")
+        if final_obs is not None and (final_obs.dtype != self.dtype or not final_obs.is_contiguous() or final_obs.numel() != self.n * capi.OBS_DIM):
+            raise ValueError("final_obs must be a contiguous [E,D,20] tensor of the env's dtype")
+        if getattr(self, "_ep_reward", None) is None:
+            self._ep_reward = torch.zeros((self.NUM_ENVS,), dtype=self._episode_dtype(), device=self.device)
+            self._ep_flags = torch.zeros((self.NUM_ENVS,), dtype=torch.int32, device=self.device)
+        capi.check(self._lib.mds_step_episodes(self._h, C.c_void_p(act.data_ptr()), C.c_void_p(self._obs.data_ptr()),
+                                               C.c_void_p(final_obs.data_ptr() if final_obs is not None else None),
+                                               C.c_void_p(self._ep_reward.data_ptr()), C.c_void_p(self._ep_flags.data_ptr()), self._stream()),
+                   "mds_step_episodes")
+        self.step_counter += self.PYB_STEPS_PER_CTRL
+        return self._obs, self._ep_reward, (self._ep_flags & 1) != 0, (self._ep_flags & 2) != 0, {"flags": self._ep_flags}
+
+    def rollout_episodes(self, actions: torch.Tensor, first_step: int, n_steps: int, obs_log: torch.Tensor | None = None,
+                         reward_log: torch.Tensor | None = None, flags_log: torch.Tensor | None = None, steps_per_launch: int = 1):
+        """``n_steps`` control steps of the replayed action table ``actions`` [A,E,D,4] with the episode rule, ``steps_per_launch`` per
+        kernel launch (mds_rollout_episodes).  Step j writes slot ``j % T`` of each log given: ``obs_log`` [T,E,D,20] (the transition's
+        rows, before any reset), ``reward_log`` [T,E] (float32; float64 on a float64 env), ``flags_log`` [T,E] int32; the logs share T.
+        Returns the current observation [E,D,20] (post-reset rows where an env was done in the last step)."""
+        self._require_open()
+        if actions.dtype != self.dtype or not actions.is_contiguous() or actions.numel() % (self.n * capi.ACT_DIM):
+            raise ValueError("actions must be a contiguous [A,E,D,4] tensor of the env's dtype")
+        slots = set()
+        for name, log, dt, per in (("obs_log", obs_log, self.dtype, self.n * capi.OBS_DIM), ("reward_log", reward_log, self._episode_dtype(), self.NUM_ENVS),
+                                   ("flags_log", flags_log, torch.int32, self.NUM_ENVS)):
+            if log is None:
+                continue
+            if log.dtype != dt or not log.is_contiguous() or log.numel() == 0 or log.numel() % per:
+                raise ValueError(f"{name} must be a contiguous tensor of dtype {dt} with {per} values per step")
+            slots.add(log.numel() // per)
+        if len(slots) > 1:
+            raise ValueError("obs_log, reward_log and flags_log must hold the same number of steps")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)   # noqa: E731
+        capi.check(self._lib.mds_rollout_episodes(self._h, ptr(actions), C.c_int(actions.numel() // (self.n * capi.ACT_DIM)), C.c_int(int(first_step)),
+                                                  C.c_int(int(n_steps)), ptr(obs_log), C.c_int(slots.pop() if slots else 0), ptr(reward_log),
+                                                  ptr(flags_log), C.c_int(int(steps_per_launch)), ptr(self._obs), self._stream()),
+                   "mds_rollout_episodes")
+        self.step_counter += n_steps * self.PYB_STEPS_PER_CTRL
+        return self._obs
+
+    def episode_counters(self):
+        """Zero-copy torch views [E] of the per-env episode counters (mds_episode_ptrs): ``length`` (int32) and ``ret`` of the running
+        episode; ``count`` (int32), ``sum_return`` and ``sum_length`` (int32) of the completed ones.  No atomics: reduce them yourself."""
+        self._require_open()
+        ptrs = (C.c_void_p * 5)()
+        capi.check(self._lib.mds_episode_ptrs(self._h, ptrs), "mds_episode_ptrs")
+
+        class _Raw:
+            def __init__(self, ptr, n, dt):
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": dt, "data": (int(ptr), False), "version": 2}
+
+        ft = "<f8" if self.dtype == torch.float64 else "<f4"
+        names = (("length", "<i4"), ("ret", ft), ("count", "<i4"), ("sum_return", ft), ("sum_length", "<i4"))
+        return {k: torch.as_tensor(_Raw(ptrs[j], self.NUM_ENVS, dt), device=self.device) for j, (k, dt) in enumerate(names)}
+
     def set_rollout_streams(self, n_streams: int = 0):
         """How rollout_geometric issues its steps: 0 auto, 1 the current stream only, 2 the two halves of the shard on two
         internal streams (mds_set_rollout_streams).  Same results either way."""
