@@ -56,7 +56,7 @@ extern "C" {
 typedef enum mds_status {
   MDS_OK = 0,
   MDS_EINVAL = -1,      /* bad argument (null pointer, size, enum) */
-  MDS_ENOMEM = -2,      /* hipMalloc failed */
+  MDS_ENOMEM = -2,      /* out of device memory (hipMalloc, from any call that allocates) or of host memory; the handle is as before the call */
   MDS_EHIP = -3,        /* a HIP runtime call failed; see mds_last_error() */
   MDS_EALIGN = -4,      /* a device pointer is not 16-byte aligned */
   MDS_ESTATE = -5,      /* call not valid in the handle's state (e.g. no trajectory set) */

@@ -13,6 +13,7 @@
 
 #include "../../include/mds.h"
 #include "mds_consts.hpp"
+#include "mds_devmem.hpp"
 #include "mds_kernels.hip"
 #include "mds_traj_image.hpp"
 #ifndef MDS_PART
@@ -66,6 +67,18 @@ int fail(int code, const char* who, const char* what) {          // "<entry poin
     if (e__ != hipSuccess) return fail_hip(e__, #call); \
   } while (0)
 
+// The one binding of the handle's allocator (mds_devmem.hpp) to the HIP runtime: every block a handle owns is allocated, zero-filled
+// and freed here and nowhere else.  Out of device memory is MDS_ENOMEM from every entry point, any other failure MDS_EHIP.
+int dev_status(hipError_t e, const char* what) {
+  if (e == hipSuccess) return MDS_OK;
+  return e == hipErrorOutOfMemory ? fail(MDS_ENOMEM, what, ": out of device memory") : fail_hip(e, what);
+}
+const DevAllocator kHipAllocator = {
+    [](void** out, size_t bytes) { return dev_status(hipMalloc(out, bytes), "hipMalloc"); },
+    [](void* p) { (void)hipFree(p); },
+    [](void* p, size_t bytes) { return dev_status(hipMemset(p, 0, bytes), "hipMemset"); },
+};
+
 size_t elem_size(int dtype) { return dtype == MDS_F64 ? 8 : (dtype == MDS_F16 ? 2 : 4); }   // MDS_F32C: fp32 buffers
 size_t comp_size(int dtype) { return dtype == MDS_F64 ? 8 : 4; }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -111,6 +124,8 @@ template <typename T> struct HostParams {
 };
 
 struct mds_handle {
+  explicit mds_handle(const DevAllocator& a) : mem(a) {}
+  DevMem mem;                    // owner of every device block behind the pointer fields below: they are allocated and freed through it alone
   mds_config cfg = {};
   mds_geometric_gains gains = {};
   double wind[3] = {0.0, 0.0, 0.0};
@@ -430,7 +445,7 @@ static void launch_linear_xdot(const Consts<T>& C, int count, const void* x, con
 
 // set-up path: (re)write one gain struct to its device copy, synchronously
 template <typename GF, typename GD> static int upload_gain(mds_handle* h, int slot, const GF& f32, const GD& f64) {
-  if (!h->gain_dev[slot]) MDS_HIP(hipMalloc(&h->gain_dev[slot], sizeof(f64)));
+  if (int rc = h->mem.alloc(&h->gain_dev[slot], sizeof(f64))) return rc;
   if (h->cfg.dtype == MDS_F64) MDS_HIP(hipMemcpy(h->gain_dev[slot], &f64, sizeof(f64), hipMemcpyHostToDevice));
   else MDS_HIP(hipMemcpy(h->gain_dev[slot], &f32, sizeof(f32), hipMemcpyHostToDevice));
   return MDS_OK;
@@ -525,7 +540,7 @@ int mds_create(const mds_config* cfg, mds_handle** out) {
     return fail(MDS_EINVAL, "mds_create: non-positive drone constant");
   DevGuard dev_guard__(cfg->device);        // the caller's current device is restored on return
   if (dev_guard__.err != hipSuccess) return fail_hip(dev_guard__.err, "mds_create: hipSetDevice(cfg->device)");
-  mds_handle* h = new (std::nothrow) mds_handle();
+  mds_handle* h = new (std::nothrow) mds_handle(kHipAllocator);
   if (!h) return fail(MDS_ENOMEM, "mds_create: host allocation");
   h->cfg = *cfg;
   mds_default_geometric_gains(&h->gains);
@@ -542,48 +557,37 @@ int mds_create(const mds_config* cfg, mds_handle** out) {
     mds_default_dslpid_gains(&dg);
     mds_set_dslpid_gains(h, &dg);
   }
-  hipError_t e = hipMalloc(&h->state, 13 * h->ld * es);
-  if (e == hipSuccess && is_comp(h)) e = hipMalloc(&h->state_lo, 4 * h->ld * es);
-  if (e == hipSuccess && is_comp(h)) e = hipMemset(h->state_lo, 0, 4 * h->ld * es);
-  if (e == hipSuccess && h->envfx) e = hipMalloc(&h->state_alt, 13 * h->ld * es);
-  if (e == hipSuccess && h->envfx) e = hipMemset(h->state_alt, 0, 13 * h->ld * es);
-  if (e == hipSuccess && h->envfx) e = hipMalloc(&h->act_scratch, (size_t)h->n * 4 * es);
-  if (e == hipSuccess) e = hipMalloc(&h->origin, 3 * h->ld * cs);
-  if (e == hipSuccess) e = hipMalloc(&h->last_rpm, 4 * h->ld * cs);
-  if (e == hipSuccess) e = hipMalloc(&h->lem, 7 * h->ld * cs);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->scratch, (size_t)h->n * 20 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&h->ll, 6 * h->ld * cs);
-  if (e == hipSuccess) e = hipMemset(h->ll, 0, 6 * h->ld * cs);
-  if (e == hipSuccess) e = hipMalloc(&h->pid, 9 * h->ld * cs);
-  if (e == hipSuccess) e = hipMemset(h->pid, 0, 9 * h->ld * cs);
-  if (e == hipSuccess) e = hipMemset(h->state, 0, 13 * h->ld * es);
-  if (e == hipSuccess) e = hipMemset(h->origin, 0, 3 * h->ld * cs);
-  if (e == hipSuccess) e = hipMemset(h->last_rpm, 0, 4 * h->ld * cs);
-  if (e == hipSuccess) e = hipMemset(h->lem, 0, 7 * h->ld * cs);
-  if (e != hipSuccess) {
-    mds_destroy(h);
-    return e == hipErrorOutOfMemory ? fail(MDS_ENOMEM, "mds_create: hipMalloc") : fail_hip(e, "mds_create");
+  std::vector<DevMem::Want> bufs = {{&h->state, 13 * h->ld * es, true},
+                                    {&h->origin, 3 * h->ld * cs, true},
+                                    {&h->last_rpm, 4 * h->ld * cs, true},
+                                    {&h->lem, 7 * h->ld * cs, true},
+                                    {&h->scratch, (size_t)h->n * 20 * sizeof(double), true},      // (zeros: the identity attitude below)
+                                    {&h->ll, 6 * h->ld * cs, true},
+                                    {&h->pid, 9 * h->ld * cs, true}};
+  if (is_comp(h)) bufs.push_back({&h->state_lo, 4 * h->ld * es, true});
+  if (h->envfx) {
+    bufs.push_back({&h->state_alt, 13 * h->ld * es, true});
+    bufs.push_back({&h->act_scratch, (size_t)h->n * 4 * es});
   }
+  int rc = h->mem.alloc_all(bufs);
   // identity attitude
-  {
-    const size_t nbytes = (size_t)h->n * 6 * sizeof(double);
-    MDS_HIP(hipMemset(h->scratch, 0, nbytes));
+  if (rc == MDS_OK) {
     with_dtype(h->cfg.dtype, [&](auto DT) {
       using T = typename decltype(DT)::T;
       using S = typename decltype(DT)::S;
       k_reset<T, S><<<grid_for(h->n, 256), 256, 0, 0>>>(h->n, h->ld, h->scratch, h->scratch + (size_t)3 * h->n, (const T*)h->origin, (S*)h->state,
                                                          (T*)h->last_rpm, 0, (S*)h->state_lo);
     });
-    MDS_HIP(hipGetLastError());
-    MDS_HIP(hipDeviceSynchronize());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) rc = fail_hip(e, "mds_create: identity attitude");
   }
   // shards large enough for the auto policy of the two-chain rollouts get their streams and events now (smallest auto
   // threshold: the CBF loop, 2^16 drones); smaller ones only if mds_set_rollout_streams(h, 2) asks for them
-  if ((size_t)h->n >= kSplitMinDrones / 4) {
-    if (int rc = split_streams_ready(h)) {
-      mds_destroy(h);
-      return rc;
-    }
+  if (rc == MDS_OK && (size_t)h->n >= kSplitMinDrones / 4) rc = split_streams_ready(h);
+  if (rc != MDS_OK) {            // every failure after `new`: the handle and whatever it owns by now go through mds_destroy
+    mds_destroy(h);
+    return rc;
   }
   *out = h;
   return MDS_OK;
@@ -592,44 +596,7 @@ int mds_create(const mds_config* cfg, mds_handle** out) {
 int mds_destroy(mds_handle* h) {
   if (!h) return MDS_OK;
   MDS_DEV(h);
-  if (h->state) (void)hipFree(h->state);
-  if (h->state_lo) (void)hipFree(h->state_lo);
-  if (h->state_alt) (void)hipFree(h->state_alt);
-  if (h->act_scratch) (void)hipFree(h->act_scratch);
-  if (h->origin) (void)hipFree(h->origin);
-  if (h->last_rpm) (void)hipFree(h->last_rpm);
-  if (h->lem) (void)hipFree(h->lem);
-  if (h->scratch) (void)hipFree(h->scratch);
-  if (h->init_pose) (void)hipFree(h->init_pose);
-  if (h->ep_image) (void)hipFree(h->ep_image);
-  if (h->ep_target) (void)hipFree(h->ep_target);
-  if (h->ep_target_world) (void)hipFree(h->ep_target_world);
-  if (h->ep_counters) (void)hipFree(h->ep_counters);
-  if (h->pair_ij) (void)hipFree(h->pair_ij);
-  if (h->obstacles) (void)hipFree(h->obstacles);
-  if (h->cbf_order) (void)hipFree(h->cbf_order);
-  if (h->cbf_count) (void)hipFree(h->cbf_count);
-  if (h->cbf_cost) (void)hipFree(h->cbf_cost);
-  for (int k = 0; k < 3; ++k)
-    if (h->gain_dev[k]) (void)hipFree(h->gain_dev[k]);
-  if (h->cbf_unom) (void)hipFree(h->cbf_unom);
-  if (h->cbf_xdes) (void)hipFree(h->cbf_xdes);
-  if (h->cbf_usafe) (void)hipFree(h->cbf_usafe);
-  if (h->ll) (void)hipFree(h->ll);
-  if (h->pid) (void)hipFree(h->pid);
-  if (h->segs) (void)hipFree(h->segs);
-  if (h->tinfo) (void)hipFree(h->tinfo);
-  if (h->fedce_P) (void)hipFree(h->fedce_P);
-  if (h->fedce_theta) (void)hipFree(h->fedce_theta);
-  if (h->dlqr_K) (void)hipFree(h->dlqr_K);
-  if (h->fo_V) (void)hipFree(h->fo_V);
-  if (h->fo_W) (void)hipFree(h->fo_W);
-  if (h->fo_theta) (void)hipFree(h->fo_theta);
-  if (h->dlqr_omega_K) (void)hipFree(h->dlqr_omega_K);
-  for (int k = 0; k < 2; ++k) {
-    if (h->care_tab[k]) (void)hipFree(h->care_tab[k]);
-    if (h->care_K64[k]) (void)hipFree(h->care_K64[k]);
-  }
+  h->mem.release_all();
   if (h->split_st) (void)hipStreamDestroy(h->split_st);
   for (int k = 0; k < 2; ++k)
     if (h->split_ev[k]) (void)hipEventDestroy(h->split_ev[k]);
@@ -693,7 +660,7 @@ int mds_reset(mds_handle* h, const double* xyz, const double* rpy, void* stream)
   if (!h || !xyz || !rpy) return fail(MDS_EINVAL, "mds_reset: null argument");
   hipStream_t st = (hipStream_t)stream;
   const size_t nb = (size_t)h->n * 3 * sizeof(double);
-  if (!h->init_pose) MDS_HIP(hipMalloc((void**)&h->init_pose, 2 * nb));
+  if (int rc = h->mem.alloc(&h->init_pose, 2 * nb)) return rc;
   MDS_HIP(hipMemcpyAsync(h->init_pose, xyz, nb, hipMemcpyHostToDevice, st));
   MDS_HIP(hipMemcpyAsync(h->init_pose + (size_t)3 * h->n, rpy, nb, hipMemcpyHostToDevice, st));
   if (int rc = launch_reset_range(h, st, 0, h->n)) return rc;
@@ -946,17 +913,16 @@ int mds_set_trajectory_segments(mds_handle* h, const double* segs, const int32_t
   const char* why = "";
   const int brc = build_traj_image(segs, offsets, compound, n, total, fm, ti, nu, &why);
   if (brc != MDS_OK) return fail(brc, why);
-  int rc = mds_set_origin(h, anchor, stream);
+  if (int rc = h->mem.alloc(&h->tinfo, sizeof(int) * 3 * n)) return rc;
+  // the new segment table is complete on the device before the one in use is given up: whatever fails on the way, the previous
+  // upload (tables, nseg_total, has_traj, traj_mode, traj_yaw_free) keeps flying
+  const int rc = h->mem.replace(&h->segs, sizeof(double) * fm.size(), [&](void* new_segs) -> int {
+    MDS_HIP(hipMemcpy(new_segs, fm.data(), sizeof(double) * fm.size(), hipMemcpyHostToDevice));
+    if (int orc = mds_set_origin(h, anchor, stream)) return orc;
+    MDS_HIP(hipMemcpy(h->tinfo, ti.data(), sizeof(int) * 3 * n, hipMemcpyHostToDevice));
+    return MDS_OK;
+  });
   if (rc != MDS_OK) return rc;
-  hipError_t e = hipSuccess;
-  if (h->segs) (void)hipFree(h->segs);
-  h->segs = nullptr;
-  h->nseg_total = 0;
-  if (!h->tinfo) e = hipMalloc((void**)&h->tinfo, sizeof(int) * 3 * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&h->segs, sizeof(double) * fm.size());
-  if (e == hipSuccess) e = hipMemcpy(h->segs, fm.data(), sizeof(double) * fm.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(h->tinfo, ti.data(), sizeof(int) * 3 * n, hipMemcpyHostToDevice);
-  if (e != hipSuccess) return fail_hip(e, "mds_set_trajectory_segments");
   h->nseg_total = nu;
   h->has_traj = true;
   h->traj_mode = 2;
@@ -1209,19 +1175,14 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   if (!h->init_pose) return fail(MDS_ESTATE, "mds_set_episodes: needs an earlier mds_reset");
   hipStream_t st = (hipStream_t)stream;
   const size_t es = elem_size(h->cfg.dtype), cs = comp_size(h->cfg.dtype), tb = (size_t)h->n * 3 * sizeof(double);
-  if (!h->ep_image) MDS_HIP(hipMalloc(&h->ep_image, 13 * h->ld * es));
-  if (!h->ep_target) MDS_HIP(hipMalloc(&h->ep_target, 4 * h->ld * cs));
-  if (!h->ep_counters) {
-    h->ep_slots = ((size_t)h->cfg.num_envs + 31) / 32 * 32;
-    MDS_HIP(hipMalloc(&h->ep_counters, 5 * h->ep_slots * 8));
-  }
+  h->ep_slots = ((size_t)h->cfg.num_envs + 31) / 32 * 32;
+  if (int rc = h->mem.alloc_all({{&h->ep_image, 13 * h->ld * es}, {&h->ep_target, 4 * h->ld * cs}, {&h->ep_counters, 5 * h->ep_slots * 8}})) return rc;
   if (target_host) {
-    if (!h->ep_target_world) MDS_HIP(hipMalloc((void**)&h->ep_target_world, tb));
+    if (int rc = h->mem.alloc(&h->ep_target_world, tb)) return rc;
     MDS_HIP(hipMemcpyAsync(h->ep_target_world, target_host, tb, hipMemcpyHostToDevice, st));
   } else if (h->ep_target_world) {
     MDS_HIP(hipStreamSynchronize(st));          // (set-up path: nothing enqueued may still read it)
-    (void)hipFree(h->ep_target_world);
-    h->ep_target_world = nullptr;
+    h->mem.release(&h->ep_target_world);
   }
   h->ep = *p;
   if (int rc = episode_build_image(h, st)) return rc;
@@ -1516,18 +1477,23 @@ int mds_cbf_configure(mds_handle* h, const mds_cbf_params* p, const double* obst
   if (h->cfg.dtype == MDS_F16) return fail(MDS_EUNSUPPORTED, "mds_cbf_configure: fp16 storage");
   if (!(p->zscale > 0) || !(p->safety_radius > 0)) return fail(MDS_EINVAL, "mds_cbf_configure: zscale / safety_radius");
   const int D = h->cfg.num_drones, npairs = D * (D - 1) / 2;
-  if (!h->pair_ij && npairs > 0) {
-    int* host = new (std::nothrow) int[npairs];
-    if (!host) return fail(MDS_ENOMEM, "mds_cbf_configure: host allocation");
+  const bool new_pairs = !h->pair_ij && npairs > 0;
+  std::vector<DevMem::Want> bufs = {{&h->obstacles, sizeof(double) * 4 * kCbfMaxObs},
+                                    {&h->cbf_order, sizeof(int) * 9 * (size_t)h->cfg.num_envs},
+                                    {&h->cbf_count, sizeof(int) * 12},
+                                    {&h->cbf_cost, sizeof(int) * (size_t)h->cfg.num_envs, true}};
+  if (new_pairs) bufs.push_back({&h->pair_ij, sizeof(int) * npairs});
+  if (int rc = h->mem.alloc_all(bufs)) return rc;
+  if (new_pairs) {
+    std::vector<int> host(npairs);
     int r = 0;
     for (int i = 0; i < D - 1; ++i)
       for (int j = i + 1; j < D; ++j) host[r++] = i | (j << 8);
-    hipError_t e = hipMalloc((void**)&h->pair_ij, sizeof(int) * npairs);
-    if (e == hipSuccess) e = hipMemcpy(h->pair_ij, host, sizeof(int) * npairs, hipMemcpyHostToDevice);
-    delete[] host;
-    if (e != hipSuccess) return fail_hip(e, "mds_cbf_configure: pair table");
+    if (hipError_t e = hipMemcpy(h->pair_ij, host.data(), sizeof(int) * npairs, hipMemcpyHostToDevice)) {
+      h->mem.release(&h->pair_ij);              // (never a table without its contents: the next call builds it again)
+      return fail_hip(e, "mds_cbf_configure: pair table");
+    }
   }
-  if (!h->obstacles) MDS_HIP(hipMalloc(&h->obstacles, sizeof(double) * 4 * kCbfMaxObs));
   if (p->n_obs > 0) {
     if (h->cfg.dtype == MDS_F64) {
       MDS_HIP(hipMemcpy(h->obstacles, obstacles, sizeof(double) * 4 * p->n_obs, hipMemcpyHostToDevice));
@@ -1536,12 +1502,6 @@ int mds_cbf_configure(mds_handle* h, const mds_cbf_params* p, const double* obst
       for (int k = 0; k < 4 * p->n_obs; ++k) tmp[k] = (float)obstacles[k];
       MDS_HIP(hipMemcpy(h->obstacles, tmp, sizeof(float) * 4 * p->n_obs, hipMemcpyHostToDevice));
     }
-  }
-  if (!h->cbf_order) MDS_HIP(hipMalloc((void**)&h->cbf_order, sizeof(int) * 9 * (size_t)h->cfg.num_envs));
-  if (!h->cbf_count) MDS_HIP(hipMalloc((void**)&h->cbf_count, sizeof(int) * 12));
-  if (!h->cbf_cost) {
-    MDS_HIP(hipMalloc((void**)&h->cbf_cost, sizeof(int) * (size_t)h->cfg.num_envs));
-    MDS_HIP(hipMemset(h->cbf_cost, 0, sizeof(int) * (size_t)h->cfg.num_envs));
   }
   h->cbf_calls = h->cbf_calls_half[0] = h->cbf_calls_half[1] = -1;   // a new problem: forget the cost classes
   {
@@ -1983,11 +1943,9 @@ int step_nominal_lowlevel(mds_handle* h, double t, void* obs, int32_t* status, v
     }
   }
   if (with_filter) h->cbf_last_step_kernel = 0;
-  if (!h->cbf_unom) {
-    MDS_HIP(hipMalloc(&h->cbf_unom, (size_t)h->n * 4 * es));
-    MDS_HIP(hipMalloc(&h->cbf_xdes, (size_t)h->n * 10 * es));
-    MDS_HIP(hipMalloc(&h->cbf_usafe, (size_t)h->n * 4 * es));
-  }
+  if (!h->cbf_unom)            // (first step only: all three or none, so that cbf_unom alone says "the scratch exists")
+    if (int rc = h->mem.alloc_all({{&h->cbf_unom, (size_t)h->n * 4 * es}, {&h->cbf_xdes, (size_t)h->n * 10 * es}, {&h->cbf_usafe, (size_t)h->n * 4 * es}}))
+      return rc;
   // drones of the env range: whole 256-drone batches (the caller of a partial range guarantees the alignment)
   if (rg.ne < 0) rg.ne = h->cfg.num_envs;
   const size_t i0 = (size_t)rg.e0 * h->cfg.num_drones, i1 = i0 + (size_t)rg.ne * h->cfg.num_drones;
@@ -2188,13 +2146,14 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
   h->cbf_last_step_kernel = 2;
   // tuning aid: MDS_TUNE_ROLL_STAMPS=1 -> per-wave shader-clock ticks by part of the step, summed over this call, printed to stderr
   // (synchronises the stream: never set it in production)
-  unsigned long long* stamps_dev = nullptr;
+  unsigned long long* stamps_base = nullptr;
+  DevMem stamps_mem(kHipAllocator);             // the call's own temporary, not the handle's: freed on every way out of this function
   const size_t n_stamp = (size_t)grid.x * nw * 10;
   if (const char* e = getenv("MDS_TUNE_ROLL_STAMPS"))
-    if (e[0] == '1') {
-      MDS_HIP(hipMalloc((void**)&stamps_dev, n_stamp * sizeof(unsigned long long) * ((n_steps + steps_per_launch - 1) / steps_per_launch)));
-    }
-  unsigned long long* const stamps_base = stamps_dev;
+    if (e[0] == '1')
+      if (int rc = stamps_mem.alloc(&stamps_base, n_stamp * sizeof(unsigned long long) * ((n_steps + steps_per_launch - 1) / steps_per_launch)))
+        return rc;
+  unsigned long long* stamps_dev = stamps_base;
   // (t advances on the host exactly as inside the kernel, one += per step, so that consecutive launches continue the same sequence)
   for (Chunks c{n_steps, steps_per_launch, t0, dt, first_slot, obs_log ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
     const int ks = c.len(), slot = c.slot;
@@ -2223,7 +2182,6 @@ int mds_rollout_cbf_geometric_fused(mds_handle* h, double t0, int n_steps, int s
     std::vector<unsigned long long> hs(n_stamp * launches);
     MDS_HIP(hipStreamSynchronize(st));
     MDS_HIP(hipMemcpy(hs.data(), stamps_base, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    (void)hipFree(stamps_base);
     static const char* part[10] = {"wait before B", "stage B", "wait after B", "stage C", "obs rows", "stage A", " B: ticket", " B: rows", " B: bookkeeping", " B: scan+solve"};
     const size_t waves = (size_t)grid.x * nw;
     double tot_mean = 0;
@@ -2279,11 +2237,8 @@ int mds_fedce_supported(const mds_config* cfg) {
 static int fedce_ready(mds_handle* h, const char* who) {
   if (!h) return fail(MDS_EINVAL, who);
   if (int rc = mds_fedce_supported(&h->cfg)) return rc;
-  if (!h->fedce_P) {
-    MDS_HIP(hipMalloc(&h->fedce_P, (size_t)h->n * 256 * sizeof(double)));
-    MDS_HIP(hipMalloc(&h->fedce_theta, (size_t)h->n * 12 * sizeof(double)));
-  }
-  return MDS_OK;
+  // both or none: fedce_P alone says "initialised" to the other entry points
+  return h->mem.alloc_all({{&h->fedce_P, (size_t)h->n * 256 * sizeof(double)}, {&h->fedce_theta, (size_t)h->n * 12 * sizeof(double)}});
 }
 
 // theta [16,12] (row-major) -> the 12 free entries (project_theta)
@@ -2395,7 +2350,7 @@ int mds_set_dlqr_gain(mds_handle* h, const double* K_host) {
   const int E = h->cfg.num_envs, D = h->cfg.num_drones;
   const size_t per = (size_t)48 * D * D, total = per * E;
   const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
-  if (!h->dlqr_K) MDS_HIP(hipMalloc(&h->dlqr_K, total * es));
+  if (int rc = h->mem.alloc(&h->dlqr_K, total * es)) return rc;
   std::vector<double> kd(h->cfg.dtype == MDS_F64 ? total : 0);
   std::vector<float> kf(h->cfg.dtype == MDS_F64 ? 0 : total);
   for (size_t e = 0; e < (size_t)E; ++e)
@@ -2492,18 +2447,9 @@ static bool fo_invert(const double* V, double* W) {
 
 static int fo_ready(mds_handle* h) {
   if (int rc = mds_fedce_supported(&h->cfg)) return rc;
-  if (!h->fo_V) {             // all three or none: fo_V alone says "initialised" to the other entry points
-    double* buf[3] = {nullptr, nullptr, nullptr};
-    const size_t bytes[3] = {(size_t)h->n * kOmegaR * kOmegaR * sizeof(double), (size_t)h->n * kOmegaR * kOmegaR * sizeof(double),
-                             (size_t)h->n * kOmegaR * kOmegaM * sizeof(double)};
-    for (int k = 0; k < 3; ++k)
-      if (hipMalloc(&buf[k], bytes[k]) != hipSuccess) {
-        for (int j = 0; j < k; ++j) (void)hipFree(buf[j]);
-        return fail(MDS_ENOMEM, "mds_fedce_omega_init: hipMalloc of the learner state failed");
-      }
-    h->fo_V = buf[0]; h->fo_W = buf[1]; h->fo_theta = buf[2];
-  }
-  return MDS_OK;
+  // all three or none: fo_V alone says "initialised" to the other entry points
+  const size_t rr = (size_t)h->n * kOmegaR * kOmegaR * sizeof(double), rm = (size_t)h->n * kOmegaR * kOmegaM * sizeof(double);
+  return h->mem.alloc_all({{&h->fo_V, rr}, {&h->fo_W, rr}, {&h->fo_theta, rm}});
 }
 
 int mds_fedce_omega_init(mds_handle* h, const double V0[169], const double theta0[117]) {
@@ -2611,7 +2557,7 @@ int mds_set_dlqr_omega_gain(mds_handle* h, const double* K_host) {
   const int E = h->cfg.num_envs, D = h->cfg.num_drones;
   const size_t per = (size_t)4 * kOmegaM * D * D, total = per * E;
   const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
-  if (!h->dlqr_omega_K) MDS_HIP(hipMalloc(&h->dlqr_omega_K, total * es));
+  if (int rc = h->mem.alloc(&h->dlqr_omega_K, total * es)) return rc;
   std::vector<double> kd(h->cfg.dtype == MDS_F64 ? total : 0);
   std::vector<float> kf(h->cfg.dtype == MDS_F64 ? 0 : total);
   for (size_t e = 0; e < (size_t)E; ++e)
@@ -2752,24 +2698,21 @@ static int care_solve_gain(mds_handle* h, const char* who, const double* Q, cons
       for (int j = 0; j < 2 * M; ++j)
         tab[q2 + ((size_t)g * 2 * M + i) * 2 * M + j] = Q[(size_t)(M * pairs.drone[g][i / M] + i % M) * nq + M * pairs.drone[g][j / M] + j % M];
   // device side: the table (uploaded only when Q or R changed: a call with the same ones only enqueues), the staging K, the gain buffer
-  if (!h->care_tab[slot]) MDS_HIP(hipMalloc(&h->care_tab[slot], ((size_t)D * 16 + (size_t)D * M * M * 2) * sizeof(double)));    // the largest a table gets
+  // (allocated before anything is uploaded or enqueued: a call that cannot get its memory changes nothing)
+  const size_t per = (size_t)nr * nq, total = per * E;
+  const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
+  void** gain = M == 12 ? &h->dlqr_K : &h->dlqr_omega_K;
+  std::vector<DevMem::Want> bufs = {{&h->care_tab[slot], ((size_t)D * 16 + (size_t)D * M * M * 2) * sizeof(double)},      // the largest a table gets
+                                    {gain, total * es, true}};                                                            // no gain yet: an env that fails keeps zeros
+  if (!K_dev) bufs.push_back({&h->care_K64[slot], total * sizeof(double)});
+  if (int rc = h->mem.alloc_all(bufs)) return rc;
+  if (!K_dev) K_dev = h->care_K64[slot];
   if (h->care_tab_host[slot] != tab) {
     MDS_HIP(hipDeviceSynchronize());
     MDS_HIP(hipMemcpy(h->care_tab[slot], tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     h->care_tab_host[slot] = tab;
   }
-  const size_t per = (size_t)nr * nq, total = per * E;
-  if (!K_dev) {
-    if (!h->care_K64[slot]) MDS_HIP(hipMalloc(&h->care_K64[slot], total * sizeof(double)));
-    K_dev = h->care_K64[slot];
-  }
-  void** gain = M == 12 ? &h->dlqr_K : &h->dlqr_omega_K;
-  const size_t es = h->cfg.dtype == MDS_F64 ? sizeof(double) : sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (!*gain) {                                  // no gain yet: an env that fails keeps zeros
-    MDS_HIP(hipMalloc(gain, total * es));
-    MDS_HIP(hipMemsetAsync(*gain, 0, total * es, st));
-  }
   MDS_HIP(hipMemsetAsync(K_dev, 0, total * sizeof(double), st));
   MDS_HIP(hipMemsetAsync(status_dev, 0, (size_t)E * sizeof(int32_t), st));
   if (iters_dev) MDS_HIP(hipMemsetAsync(iters_dev, 0, (size_t)E * sizeof(int32_t), st));

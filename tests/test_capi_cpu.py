@@ -280,6 +280,19 @@ def test_library_is_plain_c_abi_without_torch(lib):
     assert sorted(api) == header_symbols()
 
 
+def test_device_memory_goes_through_the_one_allocator_binding():
+    """csrc/mds_api.hip names the three runtime calls that create, zero-fill and free device memory once each: in the binding of the
+    handle's allocator (csrc/mds_devmem.hpp holds the rule, tests/test_devmem_cpu.py checks it).  An allocation or a free anywhere
+    else in the host layer is outside the rule."""
+    with open(os.path.join(ROOT, "multidronesim_amd", "csrc", "mds_api.hip")) as f:
+        src = f.read()
+    for call in ("hipMalloc", "hipFree", "hipMemset"):
+        sites = [m.start() for m in re.finditer(r"\b%s\w*\s*\(" % call, src) if not src[m.start():].startswith(call + "Async")]
+        lines = [src.count("\n", 0, at) + 1 for at in sites]
+        assert len(sites) == 1, (call, lines)
+        assert "kHipAllocator" in src[src.rfind("\n\n", 0, sites[0]):sites[0]], (call, lines)
+
+
 def test_create_rejects_more_than_2_30_drones(lib):
     cfg = capi.MdsConfig()
     lib.mds_default_config(capi.MDS_CF2P, C.byref(cfg))
