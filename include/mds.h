@@ -267,7 +267,7 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* params, const doub
 /* mds_rollout_step_fused's loop with episodes: step j = first_step + k applies actions_dev[j % n_action_sets], and writes into slot
  * j % log_slots of each ring that is not NULL: obs_log_dev [log_slots, n, 20] the observation the step produced (the transition's
  * result, BEFORE any reset), reward_log_dev [log_slots, E] (compute type: float, double for MDS_F64) and flags_log_dev
- * [log_slots, E] (bit 0 terminated, bit 1 truncated, bits 8..13 the OR of the drones' cause bits).  steps_per_launch control steps
+ * [log_slots, E] (bit 0 terminated, bit 1 truncated, bits 8..13 the OR of the drones' cause bits, bits 14 and 15 those of mds_set_episode_safety).  steps_per_launch control steps
  * run per kernel launch with the state in registers.  obs_dev (or NULL) receives the observation after the call's last step: the
  * CURRENT one, post-reset rows where an env was done.  Alignment as for mds_rollout_step (MDS_EALIGN); MDS_ESTATE without
  * mds_set_episodes.  Only enqueues, on the caller's stream. */
@@ -281,6 +281,32 @@ int mds_step_episodes(mds_handle* h, const void* action_dev, void* obs_dev, void
  * of the completed episodes ptrs[2] count (int32), ptrs[3] sum_return (compute type), ptrs[4] sum_length (int32).  Per env, no
  * atomics: the caller reduces.  Valid until mds_destroy. */
 int mds_episode_ptrs(mds_handle* h, void* ptrs[5]);
+
+/* COLLISION CAUSES of the per-env episodes: the safety set of the ECBF filter (mds_cbf_configure; [UPSTREAM] cbf/cbf.py custom_hdots)
+ * as a termination test on rollouts driven by raw RPM actions.  With e the separation of two drones of one env, or of a drone and a
+ * sphere obstacle,
+ *   h = (ex^2 + ey^2)^2 + (ez / zscale)^4 - Ds^4,   Ds = 2 safety_radius for a pair, safety_radius + radius for an obstacle,
+ * evaluated after every control step on the stepped (pre-reset) positions, in the handle's compute type:
+ *   cause bit 6 (flags bit 14)  a drone has an env-mate with h < 0         7 (flags bit 15)  a drone has an obstacle with h < 0
+ * Drones of different envs are never tested against each other.  A NaN h fires neither bit (bit 0 owns states that are not finite).
+ * The separation of a pair is formed from the local positions and the local-frame origins differenced separately, so it keeps the
+ * local frame's resolution far from the world origin.  Up to MDS_EPISODE_MAX_OBSTACLES spheres, world frame, one list for all envs. */
+#define MDS_EPISODE_MAX_OBSTACLES 16
+typedef struct mds_episode_safety {
+  double safety_radius, zscale;
+  int32_t n_obs, reserved;
+} mds_episode_safety;
+/* Configures (params NULL: switches off) the collision causes.  obstacles_host double [n_obs,4] = centre x, y, z, radius (NULL when
+ * n_obs is 0).  MDS_EINVAL for a safety_radius or zscale that is not finite and > 0, n_obs outside 0..MDS_EPISODE_MAX_OBSTACLES, an
+ * obstacle value that is not finite or a negative radius; MDS_ESTATE without mds_set_episodes.  mds_set_episodes(h, NULL, ..)
+ * switches the collision causes off too; a re-configuration of the episode parameters keeps them.  A failed call leaves the handle
+ * as it was.  mds_rollout_episodes / mds_step_episodes run the tests while they are configured; nothing else changes. */
+int mds_set_episode_safety(mds_handle* h, const mds_episode_safety* params, const double* obstacles_host, void* stream);
+/* Device pointers, [E] each, compute type: ptrs[0] h_min_step, the env's smallest h over all its pairs and obstacles in the last
+ * step of the most recent mds_rollout_episodes / mds_step_episodes call (pre-reset; +inf for an env with nothing to test);
+ * ptrs[1] h_min_episode, the running minimum over the env's current episode, back to +inf whenever the episode restarts (on the
+ * device, mds_reset, mds_reset_async, mds_set_episodes).  MDS_ESTATE before the first mds_set_episode_safety.  Valid until mds_destroy. */
+int mds_episode_safety_ptrs(mds_handle* h, void* ptrs[2]);
 
 /* How mds_rollout_geometric / mds_rollout_step / mds_rollout_cbf_geometric issue their steps.  Drones never read each
  * other's rows in the fused step (and a barrier row couples drones of one env only), so the two halves of the shard are

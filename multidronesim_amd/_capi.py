@@ -46,6 +46,13 @@ class MdsEpisodeParams(C.Structure):
         "z_min", "z_max", "max_dist", "max_tilt", "max_speed", "max_rate", "reward_r0", "term_penalty")]
 
 
+class MdsEpisodeSafety(C.Structure):
+    _fields_ = [("safety_radius", C.c_double), ("zscale", C.c_double), ("n_obs", C.c_int32), ("reserved", C.c_int32)]
+
+
+EPISODE_MAX_OBSTACLES = 16
+
+
 class MdsError(RuntimeError):
     def __init__(self, status, where, detail):
         super().__init__(f"{where}: {detail} (mds_status {status})")
@@ -95,6 +102,8 @@ PROTOTYPES = {
     "mds_rollout_episodes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
     "mds_step_episodes": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "mds_episode_ptrs": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    "mds_set_episode_safety": (C.c_int, [_P, C.POINTER(MdsEpisodeSafety), _PD, _P]),
+    "mds_episode_safety_ptrs": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "mds_rollout_geometric_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
     "mds_lemniscate_eval": (C.c_int, [_P, C.c_double, _P, _P]),
     "mds_geometric_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),

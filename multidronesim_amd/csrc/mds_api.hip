@@ -213,6 +213,11 @@ struct mds_handle {
   double* ep_target_world = nullptr;   // double [n,3]: the caller's targets; NULL: the reset positions
   void* ep_counters = nullptr;         // five arrays of 8-byte slots, [ep_slots] each: length | ret | count | sum_return | sum_length
   size_t ep_slots = 0;
+  // collision causes of the episodes (mds_set_episode_safety): the set as the caller gave it, and the env's smallest h
+  bool ep_safe = false;
+  mds_episode_safety ep_safety = {};
+  double ep_obstacles[4 * MDS_EPISODE_MAX_OBSTACLES] = {};
+  void* ep_hmin = nullptr;             // two arrays of 8-byte slots, [ep_slots] each: h_min_step | h_min_episode (compute type)
 };
 
 template <typename T> static inline const HostParams<T>& params(const mds_handle* h) {
@@ -649,9 +654,20 @@ static int episode_build_image(mds_handle* h, hipStream_t st) {
   MDS_HIP(hipGetLastError());
   return MDS_OK;
 }
-// the running episode of every env starts anew (length, return); the statistics of the completed ones stay
+// [first, first + count) of the two h_min arrays (0: h_min_step, 1: h_min_episode) back to +inf.  Enqueue only.
+static int episode_hmin_clear(mds_handle* h, hipStream_t st, void* block, int first, int count) {
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T;
+    const int m = (int)(h->ep_slots * count * (8 / sizeof(T)));          // the arrays are 8-byte slots whatever T is: their whole extent
+    k_episode_fill_inf<T><<<grid_for(m, 256), 256, 0, st>>>(m, (T*)((char*)block + (size_t)first * h->ep_slots * 8));
+  });
+  MDS_HIP(hipGetLastError());
+  return MDS_OK;
+}
+// the running episode of every env starts anew (length, return, smallest h); the statistics of the completed ones stay
 static int episode_restart(mds_handle* h, hipStream_t st) {
   MDS_HIP(hipMemsetAsync(h->ep_counters, 0, 2 * h->ep_slots * 8, st));
+  if (h->ep_hmin) return episode_hmin_clear(h, st, h->ep_hmin, 1, 1);
   return MDS_OK;
 }
 
@@ -1165,7 +1181,7 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_set_episodes: null handle");
   if (!p) {
-    h->ep_on = false;
+    h->ep_on = h->ep_safe = false;
     return MDS_OK;
   }
   if (p->max_steps < 0 || !(p->reward_r0 == p->reward_r0) || !(p->term_penalty == p->term_penalty))
@@ -1187,6 +1203,8 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   h->ep = *p;
   if (int rc = episode_build_image(h, st)) return rc;
   MDS_HIP(hipMemsetAsync(h->ep_counters, 0, 5 * h->ep_slots * 8, st));
+  if (h->ep_hmin)                      // the running episodes start anew: so do their minima (the safety settings themselves stay)
+    if (int rc = episode_hmin_clear(h, st, h->ep_hmin, 1, 1)) return rc;
   h->ep_on = true;
   if (target_host) MDS_HIP(hipStreamSynchronize(st));   // host buffer may be reused by the caller
   return MDS_OK;
@@ -1196,6 +1214,48 @@ int mds_episode_ptrs(mds_handle* h, void* ptrs[5]) {
   if (!h || !ptrs) return fail(MDS_EINVAL, "mds_episode_ptrs: null argument");
   if (!h->ep_counters) return fail(MDS_ESTATE, "mds_episode_ptrs: no mds_set_episodes yet");
   for (int k = 0; k < 5; ++k) ptrs[k] = (char*)h->ep_counters + (size_t)k * h->ep_slots * 8;
+  return MDS_OK;
+}
+
+static_assert(MDS_EPISODE_MAX_OBSTACLES == kEpMaxObstacles, "include/mds.h and mds_episode.hpp disagree");
+
+int mds_set_episode_safety(mds_handle* h, const mds_episode_safety* p, const double* obstacles_host, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_set_episode_safety: null handle");
+  if (!p) {
+    h->ep_safe = false;
+    return MDS_OK;
+  }
+  auto positive = [](double x) { return x > 0.0 && x < (double)INFINITY; };
+  if (!positive(p->safety_radius) || !positive(p->zscale) || p->n_obs < 0 || p->n_obs > MDS_EPISODE_MAX_OBSTACLES || (p->n_obs > 0 && !obstacles_host))
+    return fail(MDS_EINVAL, "mds_set_episode_safety: safety_radius and zscale must be finite and > 0, n_obs in 0..16 with its obstacle list");
+  for (int k = 0; k < 4 * p->n_obs; ++k) {
+    const double v = obstacles_host[k];
+    if (!(v > -(double)INFINITY && v < (double)INFINITY) || (k % 4 == 3 && v < 0.0))
+      return fail(MDS_EINVAL, "mds_set_episode_safety: an obstacle value is not finite, or a radius is negative");
+  }
+  if (!h->ep_on) return fail(MDS_ESTATE, "mds_set_episode_safety: no episodes configured (mds_set_episodes)");
+  hipStream_t st = (hipStream_t)stream;
+  // a first call allocates the two arrays; every call puts both back to +inf (a minimum over another set says nothing about this one).
+  // The handle's settings change only once that has been enqueued: a failure before leaves them, and a fresh block is given back.
+  const bool fresh = !h->ep_hmin;
+  if (int rc = h->mem.alloc(&h->ep_hmin, 2 * h->ep_slots * 8)) return rc;
+  if (int rc = episode_hmin_clear(h, st, h->ep_hmin, 0, 2)) {
+    if (fresh) h->mem.release(&h->ep_hmin);
+    return rc;
+  }
+  h->ep_safety = *p;
+  h->ep_safety.reserved = 0;
+  memset(h->ep_obstacles, 0, sizeof(h->ep_obstacles));
+  if (p->n_obs > 0) memcpy(h->ep_obstacles, obstacles_host, (size_t)p->n_obs * 4 * sizeof(double));
+  h->ep_safe = true;
+  return MDS_OK;
+}
+
+int mds_episode_safety_ptrs(mds_handle* h, void* ptrs[2]) {
+  if (!h || !ptrs) return fail(MDS_EINVAL, "mds_episode_safety_ptrs: null argument");
+  if (!h->ep_hmin) return fail(MDS_ESTATE, "mds_episode_safety_ptrs: no mds_set_episode_safety yet");
+  for (int k = 0; k < 2; ++k) ptrs[k] = (char*)h->ep_hmin + (size_t)k * h->ep_slots * 8;
   return MDS_OK;
 }
 
@@ -1224,6 +1284,17 @@ int mds_rollout_episodes(mds_handle* h, const void* actions, int n_action_sets, 
         char* cb = (char*)h->ep_counters;
         const size_t sl = h->ep_slots * 8;
         const EpisodeCounters<T> cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
+        if (h->ep_safe) {
+          EpisodeSafetyArgs<T> safe;
+          fill_episode_safety<T>(h->ep_safety.safety_radius, h->ep_safety.zscale, h->ep_safety.n_obs, h->ep_obstacles, safe.set);
+          safe.h_min_step = (T*)h->ep_hmin;
+          safe.h_min_episode = (T*)((char*)h->ep_hmin + sl);
+          k_rollout_episodes_safe<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(
+              params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
+              (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1,
+              ks, (S*)(last ? obs : nullptr), cnt, safe);
+          return;
+        }
         k_rollout_episodes<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(
             params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
             (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks,

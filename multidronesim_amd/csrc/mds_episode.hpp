@@ -9,6 +9,10 @@
 //   3  1 - 2 (qx^2 + qy^2) < cos(max_tilt)     the body z axis against world z
 //   4  |v|^2 > max_speed^2
 //   5  |w|^2 > max_rate^2
+//   6  an env-mate is inside the pair safety set: h < 0 with Ds = 2 safety_radius      (mds_set_episode_safety; off without it)
+//   7  a sphere obstacle is inside the safety set: h < 0 with Ds = safety_radius + r   (the same)
+// h is the zeroth-order barrier of the CBF filter (mds_cbf.hpp cbf_row_o2_pairs, [UPSTREAM] cbf/cbf.py custom_hdots):
+//   h = (ex^2 + ey^2)^2 + (ez / zscale)^4 - Ds^4,   e the separation.  A NaN h fires neither bit (bit 0 owns states that are not finite).
 // A threshold that is not finite or out of range switches its test off: fill_episode_rule turns it into a bound no finite value
 // crosses (and a value that is not finite is bit 0's).
 // Env: terminated = OR over its drones; truncated = !terminated and the episode has run max_steps control steps (0: never);
@@ -20,8 +24,10 @@
 
 namespace mds {
 
-constexpr int kEpTerminated = 1, kEpTruncated = 2, kEpCauseShift = 8;     // the flags word: bit 0, bit 1, cause bits at 8..13
-constexpr int kEpCauses = 6;
+constexpr int kEpTerminated = 1, kEpTruncated = 2, kEpCauseShift = 8;     // the flags word: bit 0, bit 1, cause bits at 8..15
+constexpr int kEpCauses = 8;
+constexpr int kEpCausePair = 1 << 6, kEpCauseObstacle = 1 << 7;
+constexpr int kEpMaxObstacles = 16;
 
 // the thresholds as the tests read them (word-sized: passed to the kernels by value)
 template <typename T> struct EpisodeRule {
@@ -45,6 +51,52 @@ inline void fill_episode_rule(int max_steps, double z_min, double z_max, double 
   r.term_penalty = (T)term_penalty;
   r.max_steps = max_steps > 0 ? max_steps : 0;
   r.pad = 0;
+}
+
+// the safety set as the tests read it (passed to the kernel by value: the obstacle rows are wave-uniform reads of the argument block)
+template <typename T> struct EpisodeSafety {
+  T inv_zscale, neg_ds4_pair;
+  int n_obs, pad;
+  T obs[kEpMaxObstacles][4];          // centre x, y, z (world frame), -(safety_radius + radius)^4
+};
+
+// -Ds^4 the way mds_cbf.hpp cbf_neg_ds4 forms it
+template <typename T> inline T episode_neg_ds4(T Ds) {
+  const T Ds2 = Ds * Ds;
+  return -(Ds2 * Ds2);
+}
+
+// the caller's parameters (include/mds.h mds_episode_safety; obstacles [n_obs,4] = centre xyz, radius) -> the set in T
+template <typename T> inline void fill_episode_safety(double safety_radius, double zscale, int n_obs, const double* obstacles, EpisodeSafety<T>& s) {
+  s.inv_zscale = (T)(1.0 / zscale);
+  s.neg_ds4_pair = episode_neg_ds4((T)(2.0 * safety_radius));
+  s.n_obs = n_obs;
+  s.pad = 0;
+  for (int k = 0; k < kEpMaxObstacles; ++k) {
+    const bool on = k < n_obs;
+    for (int c = 0; c < 3; ++c) s.obs[k][c] = on ? (T)obstacles[4 * k + c] : T(0);
+    s.obs[k][3] = on ? episode_neg_ds4((T)safety_radius + (T)obstacles[4 * k + 3]) : T(0);
+  }
+}
+
+// h of one separation, in the operation order of the h lines of cbf_row_o2_pairs (no contraction of s)
+template <typename T> MDS_HD T episode_barrier(T ex, T ey, T ez, T inv_zscale, T neg_ds4) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const T ex2 = ex * ex, ey2 = ey * ey;
+  const T s = ex2 + ey2;
+  const T ezc = ez * inv_zscale;
+  const T ezc2 = ezc * ezc;
+  T h = m_fma(ezc2, ezc2, neg_ds4);
+  h = m_fma(s, s, h);
+  return h;
+}
+
+// one tested separation: its cause bit into `cause` when h < 0, and h into the running minimum (a NaN h does neither)
+template <typename T> MDS_HD void episode_safety_test(T h, int bit, int& cause, T& h_min) {
+  cause |= (h < T(0)) ? bit : 0;
+  h_min = (h < h_min) ? h : h_min;
 }
 
 // the cause bits of one drone.  p: position in the frame `home` is given in; world_z: the same drone's world height

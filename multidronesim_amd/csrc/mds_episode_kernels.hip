@@ -13,6 +13,15 @@
 // write_obs_rows needs a wave's rows to be one contiguous span starting at i - lane (they are: 64 consecutive threads, consecutive
 // drones), bounded by its `n` argument (the block's end), and, for the 40-byte fp16 rows, an even first drone in every wave: the
 // envs per block are chosen so that envs * D is even.
+//
+// k_rollout_episodes_safe is k_rollout_episodes with the collision causes of mds_set_episode_safety (bits 6 and 7, the env's smallest
+// h).  The drones of an env already share a workgroup, so the pairwise test is one more exchange through LDS: positions out, barrier,
+// the D - 1 env-mates read back.  That makes two barriers per step and lets every exchanged array stay single-buffered (the argument
+// stands in the kernel).  It is a sibling kernel, not a flag of the first: a body shared through an inlined function reads the
+// by-value argument blocks differently, and the instructions of the existing kernel were to stay as they are
+// (profiles/asm_equiv_episode_safety.md).  Its loop is the first kernel's line for line, with the SAFE blocks added; a change to one
+// is a change to both.  LDS of the sibling: observation staging + 5 words (cause, term, h) + 3 position and 3 origin words per lane
+// = 58 368 B in float64, 29 696 B in float32, 19 456 B with fp16 storage.
 #include "mds_episode.hpp"
 
 namespace mds {
@@ -136,6 +145,160 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes(const Consts<T> c, 
     if (d == 0) {
       cnt.length[e] = length; cnt.ret[e] = ret;
       cnt.count[e] = count; cnt.sum_return[e] = sum_return; cnt.sum_length[e] = sum_length;
+    }
+  }
+}
+
+// p[0 .. n) = +inf: h_min_step / h_min_episode of an env with nothing tested yet
+template <typename T> __global__ void k_episode_fill_inf(const int n, T* __restrict__ p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = T(INFINITY);
+}
+
+// what the sibling kernel takes besides: the set, and the two per-env outputs [E] (mds_episode_safety_ptrs)
+template <typename T> struct EpisodeSafetyArgs {
+  EpisodeSafety<T> set;
+  T* h_min_step;
+  T* h_min_episode;
+};
+
+// One lane's tests of a step: its stepped position against the D - 1 env-mates' (lanes b .. b + D - 1 of the position and origin arrays
+// in LDS) and against the obstacles; the bits into `cause`, the smallest h returned.
+template <typename T>
+__device__ __forceinline__ T episode_safety_lane(const EpisodeSafety<T>& set, const T* pos_x, const T* pos_y, const T* pos_z, const T* org_x,
+                                                 const T* org_y, const T* org_z, int b, int d, int D, V3<T> p, V3<T> org, int& cause) {
+  T h_lane = T(INFINITY);
+  for (int j = 0; j < D; ++j) {
+    if (j == d) continue;
+    // local parts and origin parts differenced separately (env_substep's downwash does the same): a far origin keeps the resolution
+    const T ex = (pos_x[b + j] - p.x) + (org_x[b + j] - org.x);
+    const T ey = (pos_y[b + j] - p.y) + (org_y[b + j] - org.y);
+    const T ez = (pos_z[b + j] - p.z) + (org_z[b + j] - org.z);
+    episode_safety_test(episode_barrier(ex, ey, ez, set.inv_zscale, set.neg_ds4_pair), kEpCausePair, cause, h_lane);
+  }
+  for (int m = 0; m < set.n_obs; ++m) {                      // (wave-uniform rows of the argument block)
+    const T ex = p.x - (set.obs[m][0] - org.x);
+    const T ey = p.y - (set.obs[m][1] - org.y);
+    const T ez = p.z - (set.obs[m][2] - org.z);
+    episode_safety_test(episode_barrier(ex, ey, ez, set.inv_zscale, set.obs[m][3]), kEpCauseObstacle, cause, h_lane);
+  }
+  return h_lane;
+}
+
+template <typename T, typename S, bool RK4, bool DRAG>
+__global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T> c, const EpisodeRule<T> rule, const int n, const size_t ld,
+                                                                  const int D, const int envs_per_block, S* __restrict__ state,
+                                                                  const S* __restrict__ image, const T* __restrict__ origin,
+                                                                  const T* __restrict__ target, T* __restrict__ last_rpm,
+                                                                  const S* __restrict__ actions, int a0, const int n_sets, S* __restrict__ obs_log,
+                                                                  T* __restrict__ reward_log, int* __restrict__ flags_log, int s0, const int n_slots,
+                                                                  const int n_steps, S* __restrict__ obs_now, const EpisodeCounters<T> cnt,
+                                                                  const EpisodeSafetyArgs<T> safe) {
+  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  __shared__ int red_cause[kBlock];
+  __shared__ T red_term[kBlock], red_h[kBlock];
+  __shared__ T pos_x[kBlock], pos_y[kBlock], pos_z[kBlock], org_x[kBlock], org_y[kBlock], org_z[kBlock];
+  const int tid = (int)threadIdx.x;
+  const int per_block = envs_per_block * D;
+  const int first = (int)blockIdx.x * per_block;
+  const int i = first + tid;
+  const int block_end = min(first + per_block, n);          // n = E * D: whole envs
+  const bool valid = tid < per_block && i < n;
+  const int le = tid / D, d = tid - le * D;                 // env within the block, drone within the env
+  const int E = n / D, e = (int)blockIdx.x * envs_per_block + le;
+  const int b = tid - d;                                    // the env's first lane: lanes b .. b + D - 1 are its drones, valid when this one is
+  State<T> s;
+  Resid<T> r;
+  resid_zero(r);
+  V3<T> org = {T(0), T(0), T(0)}, home = org, tgt = org;
+  T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
+  int length = 0, count = 0, sum_length = 0;
+  T ret = T(0), sum_return = T(0);
+  T h_step = T(INFINITY), h_episode = T(INFINITY);          // the env's smallest h of the last step, and of its running episode
+  if (valid) {
+    load_state<S, T>(state, ld, i, s);
+    org = load_origin(origin, ld, i);
+    home = {(T)image[sidx(0, i, ld)], (T)image[sidx(1, i, ld)], (T)image[sidx(2, i, ld)]};
+    tgt = load_origin(target, ld, i);
+    if (DRAG)
+      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
+    length = cnt.length[e]; ret = cnt.ret[e];
+    count = cnt.count[e]; sum_return = cnt.sum_return[e]; sum_length = cnt.sum_length[e];
+    h_episode = safe.h_min_episode[e];
+    org_x[tid] = org.x; org_y[tid] = org.y; org_z[tid] = org.z;   // constant over the launch: staged once, published by barrier A of step 0
+  }
+  for (int k = 0; k < n_steps; ++k) {
+    T o[kObsDim];
+    int cause = 0;
+    T term = T(0), h_lane = T(INFINITY);
+    if (valid) {
+      T act[4];
+      load4<S, T>(actions + ((size_t)a0 * n + i) * 4, act);
+      aviary_step_any<T, RK4, DRAG, false>(c, s, r, act, prev, clipped);
+      if (obs_log != nullptr) pack_obs(s, org, clipped, o);
+      cause = episode_causes(rule, s, s.p.z + org.z, home);
+      term = episode_reward_term(rule, s.p, tgt);
+      pos_x[tid] = s.p.x; pos_y[tid] = s.p.y; pos_z[tid] = s.p.z;           // the stepped, pre-reset local position
+    }
+    // the logged row is the transition's result: before any reset
+    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, block_end, i, valid, o);
+    // Two barriers per step.  A: every lane has published its position.  B: every lane has published its cause word, reward term and
+    // smallest h.  pos_* is written before A and read between A and B; red_* is written between A and B and read after B.  A wave
+    // writes pos_* of step k + 1 only after it has passed B of step k, which every wave reaches after its pos_* reads of step k; it
+    // writes red_* of step k + 1 only after A of step k + 1, which every wave reaches after its red_* reads of step k.  So no word is
+    // overwritten while a wave one barrier behind still reads it, and no array needs a parity copy.  org_* is written once, before
+    // the first A, and only read afterwards.  (write_obs_rows stages within a wave: it takes no part in this.)
+    __syncthreads();                                                         // A
+    if (valid) h_lane = episode_safety_lane(safe.set, pos_x, pos_y, pos_z, org_x, org_y, org_z, b, d, D, s.p, org, cause);
+    red_cause[tid] = cause;
+    red_term[tid] = term;
+    red_h[tid] = h_lane;
+    __syncthreads();                                                         // B
+    if (valid) {
+      int causes = 0;
+      T sum = T(0);
+      h_step = T(INFINITY);
+      for (int j = 0; j < D; ++j) {                          // drone order d = 0 .. D-1
+        causes |= red_cause[b + j];
+        sum += red_term[b + j];
+        h_step = m_min(red_h[b + j], h_step);
+      }
+      h_episode = m_min(h_step, h_episode);
+      ++length;
+      const int flags = episode_flags(rule, causes, length);
+      const T reward = episode_reward(rule, sum, flags);
+      ret += reward;
+      if (d == 0) {
+        if (reward_log != nullptr) reward_log[(size_t)s0 * E + e] = reward;
+        if (flags_log != nullptr) flags_log[(size_t)s0 * E + e] = flags;
+      }
+      if (flags & (kEpTerminated | kEpTruncated)) {
+        ++count;
+        sum_return += ret;
+        sum_length += length;
+        length = 0;
+        ret = T(0);
+        h_episode = T(INFINITY);
+        load_state<S, T>(image, ld, i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
+        for (int j = 0; j < 4; ++j) prev[j] = clipped[j] = T(0);
+      }
+    }
+    a0 = a0 + 1 == n_sets ? 0 : a0 + 1;
+    s0 = s0 + 1 == n_slots ? 0 : s0 + 1;
+  }
+  if (obs_now != nullptr) {                                  // the current observation: after the resets
+    T o[kObsDim];
+    if (valid) pack_obs(s, org, clipped, o);
+    write_obs_rows<S, T>(lds, obs_now, block_end, i, valid, o);
+  }
+  if (valid) {
+    store_state<S, T>(state, ld, i, s);
+    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
+    if (d == 0) {
+      cnt.length[e] = length; cnt.ret[e] = ret;
+      cnt.count[e] = count; cnt.sum_return[e] = sum_return; cnt.sum_length[e] = sum_length;
+      if (n_steps > 0) safe.h_min_step[e] = h_step;
+      safe.h_min_episode[e] = h_episode;
     }
   }
 }

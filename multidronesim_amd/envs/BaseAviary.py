@@ -442,7 +442,8 @@ class BaseAviary:
         """One control step with the episode rule (mds_step_episodes): ``(obs, reward[E], terminated[E], truncated[E], info)``, device
         tensors.  ``obs`` is what a policy acts on next: the rows of a done env are its post-reset observation; ``final_obs``
         (optional [E,D,20] tensor) receives the transition's own rows.  ``info["flags"]``: the int32 flags word per env (bit 0
-        terminated, bit 1 truncated, bits 8..13 the causes).  The returned tensors are reused by the next call."""
+        terminated, bit 1 truncated, bits 8..13 the causes; with ``set_episode_safety`` bit 14: two drones of the env inside the pair
+        safety set, bit 15: a drone inside an obstacle's).  The returned tensors are reused by the next call."""
         self._require_open()
         act = to_device(action, self.device, self.dtype)
         if act.numel() != self.n * capi.ACT_DIM or not act.is_contiguous():
@@ -500,6 +501,38 @@ class BaseAviary:
         ft = "<f8" if self.dtype == torch.float64 else "<f4"
         names = (("length", "<i4"), ("ret", ft), ("count", "<i4"), ("sum_return", ft), ("sum_length", "<i4"))
         return {k: torch.as_tensor(_Raw(ptrs[j], self.NUM_ENVS, dt), device=self.device) for j, (k, dt) in enumerate(names)}
+
+    def set_episode_safety(self, safety_radius: float = 0.0, zscale: float = 2.0, obstacles=None, enabled: bool = True):
+        """Collision causes of the per-env episodes (mds_set_episode_safety; needs ``set_episodes`` first): after every control step
+        each drone is tested against the other drones of its env (``Ds = 2 safety_radius``) and against the sphere ``obstacles``
+        [n_obs,4] = centre xyz in the world frame, radius (``Ds = safety_radius + radius``; at most 16, one list for all envs) on the
+        CBF filter's zeroth-order barrier ``h = (ex^2 + ey^2)^2 + (ez / zscale)^4 - Ds^4``; ``h < 0`` terminates the env with flags bit
+        14 (pair) or 15 (obstacle).  ``enabled=False`` switches the tests off; so does ``set_episodes(enabled=False)``."""
+        self._require_open()
+        if not enabled:
+            capi.check(self._lib.mds_set_episode_safety(self._h, None, None, self._stream()), "mds_set_episode_safety")
+            return
+        obs = None
+        if obstacles is not None and np.size(obstacles):
+            obs = np.ascontiguousarray(np.asarray(obstacles, dtype=np.float64).reshape(-1, 4))
+        p = capi.MdsEpisodeSafety(float(safety_radius), float(zscale), 0 if obs is None else obs.shape[0], 0)
+        capi.check(self._lib.mds_set_episode_safety(self._h, C.byref(p), capi.as_double_ptr(obs) if obs is not None else None, self._stream()),
+                   "mds_set_episode_safety")
+
+    def episode_safety(self):
+        """Zero-copy torch views [E] of the safety signal (mds_episode_safety_ptrs), in the compute type: ``h_min_step``, the env's
+        smallest ``h`` over all its pairs and obstacles in the last step of the most recent call (pre-reset; ``+inf`` with nothing to
+        test), and ``h_min_episode``, the running minimum over the env's current episode (``+inf`` again when it restarts)."""
+        self._require_open()
+        ptrs = (C.c_void_p * 2)()
+        capi.check(self._lib.mds_episode_safety_ptrs(self._h, ptrs), "mds_episode_safety_ptrs")
+
+        class _Raw:
+            def __init__(self, ptr, n, dt):
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": dt, "data": (int(ptr), False), "version": 2}
+
+        ft = "<f8" if self.dtype == torch.float64 else "<f4"
+        return {k: torch.as_tensor(_Raw(ptrs[j], self.NUM_ENVS, ft), device=self.device) for j, k in enumerate(("h_min_step", "h_min_episode"))}
 
     def set_rollout_streams(self, n_streams: int = 0):
         """How rollout_geometric issues its steps: 0 auto, 1 the current stream only, 2 the two halves of the shard on two
