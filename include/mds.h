@@ -308,6 +308,37 @@ int mds_set_episode_safety(mds_handle* h, const mds_episode_safety* params, cons
  * device, mds_reset, mds_reset_async, mds_set_episodes).  MDS_ESTATE before the first mds_set_episode_safety.  Valid until mds_destroy. */
 int mds_episode_safety_ptrs(mds_handle* h, void* ptrs[2]);
 
+/* RANDOMISED EPISODE STARTS from a counter-based generator on the device (multidronesim_amd/csrc/mds_episode_random.hpp).  While
+ * configured, a done env's drones go back not to the fixed reset image but to a start drawn around it.  The draw is a PURE FUNCTION of
+ *   (seed, g, ordinal, generation):   g = first_env * D + i, the drone's index in the whole env set;
+ *                                     ordinal = the env's `count` (mds_episode_ptrs ptrs[2], read as uint32; in the kernel the value
+ *                                               after the increment for the episode that just ended);
+ *                                     generation = 0 after mds_set_episode_randomisation, + 1 with every mds_reset_episodes,
+ * namely Philox4x32-10 with key (seed low word, seed high word) on the counters (g, ordinal, b, generation), b = 0, 1, 2, whose
+ * twelve words serve, in order, position x y z | roll pitch yaw | world velocity x y z | body rates x y z.  A word x gives
+ * s = (2 (x >> 8) + 1 - 2^24) 2^-24 in (-1, 1) -- the same 24-bit value in every compute type -- and the offset s * half_width.
+ * So a start depends neither on steps_per_launch, nor on the thread mapping, nor on how the env set is sharded over handles, and a
+ * caller who writes `count` through the zero-copy pointer thereby chooses the draws.
+ *   position  the image's + offset (local frame)       attitude  quat_from_euler(the rpy of the last mds_reset + offset); the
+ *   velocity, body rates  the offsets                            image's quaternion when the three rpy half-widths are 0
+ * each rounded through the storage type, RPM echo zero.  All half-widths 0 is the plain reset, bit for bit.  (|rpy of the reset| +
+ * half-width is meant to stay within 2 pi: the float sincos of the half angle reduces from about [-pi, pi].)  The home of cause bit
+ * 2 and the default target stay the nominal reset position: max_dist measures from the centre of the spawn box. */
+typedef struct mds_episode_randomisation {
+  uint64_t seed;
+  int64_t first_env;          /* global index of this handle's env 0 (a shard of a larger env set); 0 for a whole set */
+  double pos[3], rpy[3], vel[3], rate[3];   /* half-widths: m, rad, m/s (world), rad/s (body) */
+} mds_episode_randomisation;
+/* Configures (params NULL: switches off) the randomised starts and sets generation to 0; touches no state and no counter.
+ * MDS_EINVAL for a half-width that is not finite or negative, first_env < 0, or (first_env + E) * D beyond uint32; MDS_ESTATE without
+ * mds_set_episodes.  mds_set_episodes(h, NULL, ..) switches it off too; a re-configuration of the episode parameters, mds_reset and
+ * mds_reset_async keep it (the two resets still write the nominal poses).  A failed call leaves the handle as it was. */
+int mds_set_episode_randomisation(mds_handle* h, const mds_episode_randomisation* params, void* stream);
+/* generation + 1, then every drone to its drawn start with ordinal = its env's current `count`, zero RPM echo, every env's running
+ * episode restarted (length, return, h_min_episode; the statistics of the completed ones stay), and the current observation rows to
+ * obs_dev [n,20] unless NULL (MDS_EALIGN as for mds_get_obs).  MDS_ESTATE when randomisation is not configured.  Only enqueues. */
+int mds_reset_episodes(mds_handle* h, void* obs_dev, void* stream);
+
 /* How mds_rollout_geometric / mds_rollout_step / mds_rollout_cbf_geometric issue their steps.  Drones never read each
  * other's rows in the fused step (and a barrier row couples drones of one env only), so the two halves of the shard are
  * independent step chains: on two internal streams one half's load/store bursts fill the other's compute phase, and the

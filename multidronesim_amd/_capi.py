@@ -53,6 +53,10 @@ class MdsEpisodeSafety(C.Structure):
 EPISODE_MAX_OBSTACLES = 16
 
 
+class MdsEpisodeRandomisation(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_env", C.c_int64)] + [(k, C.c_double * 3) for k in ("pos", "rpy", "vel", "rate")]
+
+
 class MdsError(RuntimeError):
     def __init__(self, status, where, detail):
         super().__init__(f"{where}: {detail} (mds_status {status})")
@@ -104,6 +108,8 @@ PROTOTYPES = {
     "mds_episode_ptrs": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "mds_set_episode_safety": (C.c_int, [_P, C.POINTER(MdsEpisodeSafety), _PD, _P]),
     "mds_episode_safety_ptrs": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    "mds_set_episode_randomisation": (C.c_int, [_P, C.POINTER(MdsEpisodeRandomisation), _P]),
+    "mds_reset_episodes": (C.c_int, [_P, _P, _P]),
     "mds_rollout_geometric_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
     "mds_lemniscate_eval": (C.c_int, [_P, C.c_double, _P, _P]),
     "mds_geometric_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -218,6 +218,11 @@ struct mds_handle {
   mds_episode_safety ep_safety = {};
   double ep_obstacles[4 * MDS_EPISODE_MAX_OBSTACLES] = {};
   void* ep_hmin = nullptr;             // two arrays of 8-byte slots, [ep_slots] each: h_min_step | h_min_episode (compute type)
+  // randomised episode starts (mds_set_episode_randomisation): the parameters as the caller gave them (they travel to the kernels by
+  // value) and the generation word of the draw, 0 at configuration, + 1 with every mds_reset_episodes
+  bool ep_random = false;
+  mds_episode_randomisation ep_rand = {};
+  uint32_t ep_generation = 0;
 };
 
 template <typename T> static inline const HostParams<T>& params(const mds_handle* h) {
@@ -455,6 +460,18 @@ template <typename GF, typename GD> static int upload_gain(mds_handle* h, int sl
   else MDS_HIP(hipMemcpy(h->gain_dev[slot], &f32, sizeof(f32), hipMemcpyHostToDevice));
   return MDS_OK;
 }
+
+#if MDS_PART & 1
+// the handle's randomisation as the kernels take it
+template <typename T> static EpisodeRandomArgs<T> episode_random_args(const mds_handle* h) {
+  const mds_episode_randomisation& p = h->ep_rand;
+  EpisodeRandomArgs<T> a;
+  fill_episode_random<T>(p.seed, (uint32_t)((unsigned long long)p.first_env * (unsigned long long)h->cfg.num_drones), h->ep_generation, p.pos,
+                         p.rpy, p.vel, p.rate, a.set);
+  a.rpy0 = h->init_pose + (size_t)3 * h->n;
+  return a;
+}
+#endif
 
 extern "C" {
 
@@ -1181,7 +1198,7 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_set_episodes: null handle");
   if (!p) {
-    h->ep_on = h->ep_safe = false;
+    h->ep_on = h->ep_safe = h->ep_random = false;
     return MDS_OK;
   }
   if (p->max_steps < 0 || !(p->reward_r0 == p->reward_r0) || !(p->term_penalty == p->term_penalty))
@@ -1259,6 +1276,47 @@ int mds_episode_safety_ptrs(mds_handle* h, void* ptrs[2]) {
   return MDS_OK;
 }
 
+int mds_set_episode_randomisation(mds_handle* h, const mds_episode_randomisation* p, void* stream) {
+  (void)stream;                        // (nothing is enqueued: the parameters travel with the launches)
+  if (!h) return fail(MDS_EINVAL, "mds_set_episode_randomisation: null handle");
+  if (!p) {
+    h->ep_random = false;
+    return MDS_OK;
+  }
+  const double* groups[4] = {p->pos, p->rpy, p->vel, p->rate};
+  for (const double* g : groups)
+    for (int k = 0; k < 3; ++k)
+      if (!(g[k] >= 0.0 && g[k] < (double)INFINITY))
+        return fail(MDS_EINVAL, "mds_set_episode_randomisation: a half-width is not finite or is negative");
+  // g = first_env * D + i is a 32-bit counter word: the whole shard must fit
+  const unsigned long long E = (unsigned long long)h->cfg.num_envs, D = (unsigned long long)h->cfg.num_drones;
+  if (p->first_env < 0 || (unsigned long long)p->first_env > 0xFFFFFFFFull || ((unsigned long long)p->first_env + E) * D > 0xFFFFFFFFull)
+    return fail(MDS_EINVAL, "mds_set_episode_randomisation: first_env < 0, or (first_env + num_envs) * num_drones does not fit 32 bits");
+  if (!h->ep_on) return fail(MDS_ESTATE, "mds_set_episode_randomisation: no episodes configured (mds_set_episodes)");
+  h->ep_rand = *p;
+  h->ep_generation = 0;
+  h->ep_random = true;
+  return MDS_OK;
+}
+
+int mds_reset_episodes(mds_handle* h, void* obs, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_reset_episodes: null handle");
+  if (!aligned16(obs)) return fail(MDS_EALIGN, "mds_reset_episodes: obs_dev");
+  if (!h->ep_on || !h->ep_random) return fail(MDS_ESTATE, "mds_reset_episodes: no randomisation configured (mds_set_episode_randomisation)");
+  hipStream_t st = (hipStream_t)stream;
+  ++h->ep_generation;
+  with_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    k_episode_reset_random<T, S><<<grid_for(h->n, kBlock), kBlock, 0, st>>>(
+        h->n, h->ld, h->cfg.num_drones, episode_random_args<T>(h), (const int*)((char*)h->ep_counters + 2 * h->ep_slots * 8),
+        (const S*)h->ep_image, (const T*)h->origin, (S*)h->state, (T*)h->last_rpm, (S*)obs);
+  });
+  MDS_HIP(hipGetLastError());
+  h->rpm_stale = false;
+  return episode_restart(h, st);
+}
+
 int mds_rollout_episodes(mds_handle* h, const void* actions, int n_action_sets, int first_step, int n_steps, void* obs_log, int log_slots,
                          void* reward_log, int32_t* flags_log, int steps_per_launch, void* obs, void* stream) {
   MDS_DEV(h);
@@ -1284,21 +1342,27 @@ int mds_rollout_episodes(mds_handle* h, const void* actions, int n_action_sets, 
         char* cb = (char*)h->ep_counters;
         const size_t sl = h->ep_slots * 8;
         const EpisodeCounters<T> cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
+        // one launch, whichever of the four kernels: `extra` is what follows the counters (nothing | the safety set | the
+        // randomisation | both, in this order)
+        auto launch = [&](auto kernel, auto... extra) {
+          kernel<<<grid, kBlock, 0, st>>>(params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin,
+                                          (const T*)h->ep_target, (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log,
+                                          (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks, (S*)(last ? obs : nullptr), cnt, extra...);
+        };
+        using R = EpisodeRandomArgs<T>;
+        R rnd = {};
+        if (h->ep_random) rnd = episode_random_args<T>(h);
         if (h->ep_safe) {
           EpisodeSafetyArgs<T> safe;
           fill_episode_safety<T>(h->ep_safety.safety_radius, h->ep_safety.zscale, h->ep_safety.n_obs, h->ep_obstacles, safe.set);
           safe.h_min_step = (T*)h->ep_hmin;
           safe.h_min_episode = (T*)((char*)h->ep_hmin + sl);
-          k_rollout_episodes_safe<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(
-              params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
-              (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1,
-              ks, (S*)(last ? obs : nullptr), cnt, safe);
+          if (h->ep_random) launch(k_rollout_episodes_safe<T, S, RK4(), DRAG(), R>, safe, rnd);
+          else launch(k_rollout_episodes_safe<T, S, RK4(), DRAG()>, safe);
           return;
         }
-        k_rollout_episodes<T, S, RK4(), DRAG()><<<grid, kBlock, 0, st>>>(
-            params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
-            (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks,
-            (S*)(last ? obs : nullptr), cnt);
+        if (h->ep_random) launch(k_rollout_episodes<T, S, RK4(), DRAG(), R>, rnd);
+        else launch(k_rollout_episodes<T, S, RK4(), DRAG()>);
       });
     }, rk4, drag);
   }

@@ -23,6 +23,7 @@
 // is a change to both.  LDS of the sibling: observation staging + 5 words (cause, term, h) + 3 position and 3 origin words per lane
 // = 58 368 B in float64, 29 696 B in float32, 19 456 B with fp16 storage.
 #include "mds_episode.hpp"
+#include "mds_episode_random.hpp"
 
 namespace mds {
 
@@ -52,13 +53,53 @@ __global__ void k_episode_targets(const int n, const size_t ld, const double* __
     target[k * ld + i] = target_world ? (T)(target_world[3 * (size_t)i + k] - (double)origin[k * ld + i]) : (T)image[sidx(k, i, ld)];
 }
 
-template <typename T, typename S, bool RK4, bool DRAG>
+// Randomised starts (mds_set_episode_randomisation; the draw: mds_episode_random.hpp).  What the randomised forms of the two rollout
+// kernels take besides: the set, and the drones' initial Euler angles (double [n,3]: the handle's init_pose).
+template <typename T> struct EpisodeRandomArgs {
+  EpisodeRandom<T> set;
+  const double* rpy0;
+};
+// s: the image's state of drone i, just loaded -> the start drawn for the episode of its env that follows `count` completed ones
+template <typename S, typename T>
+__device__ __forceinline__ void episode_random_reset(const EpisodeRandomArgs<T>& a, int i, int count, State<T>& s) {
+  episode_random_start<S, T>(a.set, a.set.first + (uint32_t)i, (uint32_t)count, a.rpy0 + 3 * (size_t)i, s);
+}
+
+// mds_reset_episodes: every drone to the start drawn for its env's current `count`, zero RPM echo, and (obs != NULL) its observation
+// row.  Flat mapping: it keeps no per-env value, and the draw does not depend on the mapping.
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void k_episode_reset_random(const int n, const size_t ld, const int D, const EpisodeRandomArgs<T> rnd,
+                                                                 const int* __restrict__ count, const S* __restrict__ image,
+                                                                 const T* __restrict__ origin, S* __restrict__ state, T* __restrict__ last_rpm,
+                                                                 S* __restrict__ obs) {
+  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = i < n;
+  T o[kObsDim];
+  if (valid) {
+    State<T> s;
+    load_state<S, T>(image, ld, i, s);
+    episode_random_reset<S, T>(rnd, i, count[i / D], s);
+    store_state<S, T>(state, ld, i, s);
+    const T rpm[4] = {T(0), T(0), T(0), T(0)};
+    for (int k = 0; k < 4; ++k) last_rpm[k * ld + i] = rpm[k];
+    if (obs != nullptr) pack_obs(s, load_origin(origin, ld, i), rpm, o);
+  }
+  if (obs != nullptr) write_obs_rows<S, T>(lds, obs, n, i, valid, o);
+}
+
+// The trailing pack RND is empty -- the kernel of a handle without randomisation, argument for argument what it was before the pack
+// existed -- or one EpisodeRandomArgs<T>: the reset arm then moves the image's state by the draw.  The arm runs only in waves where a
+// lane is done (the branch is skipped on an empty mask), at a point where the stepped state is dead: the 3 x 40 integer multiplies of
+// the three Philox blocks stay off the ordinary step.
+template <typename T, typename S, bool RK4, bool DRAG, typename... RND>
 __global__ __launch_bounds__(kBlock) void k_rollout_episodes(const Consts<T> c, const EpisodeRule<T> rule, const int n, const size_t ld, const int D,
                                                              const int envs_per_block, S* __restrict__ state, const S* __restrict__ image,
                                                              const T* __restrict__ origin, const T* __restrict__ target, T* __restrict__ last_rpm,
                                                              const S* __restrict__ actions, int a0, const int n_sets, S* __restrict__ obs_log,
                                                              T* __restrict__ reward_log, int* __restrict__ flags_log, int s0, const int n_slots,
-                                                             const int n_steps, S* __restrict__ obs_now, const EpisodeCounters<T> cnt) {
+                                                             const int n_steps, S* __restrict__ obs_now, const EpisodeCounters<T> cnt,
+                                                             const RND... rnd) {
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
   __shared__ int red_cause[2][kBlock];
   __shared__ T red_term[2][kBlock];
@@ -128,6 +169,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes(const Consts<T> c, 
         length = 0;
         ret = T(0);
         load_state<S, T>(image, ld, i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
+        if constexpr (sizeof...(RND) != 0) episode_random_reset<S, T>(rnd..., i, count, s);      // ... moved by the episode's draw
         for (int j = 0; j < 4; ++j) prev[j] = clipped[j] = T(0);
       }
     }
@@ -185,7 +227,7 @@ __device__ __forceinline__ T episode_safety_lane(const EpisodeSafety<T>& set, co
   return h_lane;
 }
 
-template <typename T, typename S, bool RK4, bool DRAG>
+template <typename T, typename S, bool RK4, bool DRAG, typename... RND>
 __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T> c, const EpisodeRule<T> rule, const int n, const size_t ld,
                                                                   const int D, const int envs_per_block, S* __restrict__ state,
                                                                   const S* __restrict__ image, const T* __restrict__ origin,
@@ -193,7 +235,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T
                                                                   const S* __restrict__ actions, int a0, const int n_sets, S* __restrict__ obs_log,
                                                                   T* __restrict__ reward_log, int* __restrict__ flags_log, int s0, const int n_slots,
                                                                   const int n_steps, S* __restrict__ obs_now, const EpisodeCounters<T> cnt,
-                                                                  const EpisodeSafetyArgs<T> safe) {
+                                                                  const EpisodeSafetyArgs<T> safe, const RND... rnd) {
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
   __shared__ int red_cause[kBlock];
   __shared__ T red_term[kBlock], red_h[kBlock];
@@ -280,6 +322,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T
         ret = T(0);
         h_episode = T(INFINITY);
         load_state<S, T>(image, ld, i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
+        if constexpr (sizeof...(RND) != 0) episode_random_reset<S, T>(rnd..., i, count, s);      // ... moved by the episode's draw
         for (int j = 0; j < 4; ++j) prev[j] = clipped[j] = T(0);
       }
     }

@@ -534,6 +534,30 @@ class BaseAviary:
         ft = "<f8" if self.dtype == torch.float64 else "<f4"
         return {k: torch.as_tensor(_Raw(ptrs[j], self.NUM_ENVS, ft), device=self.device) for j, k in enumerate(("h_min_step", "h_min_episode"))}
 
+    def set_episode_randomisation(self, seed: int = 0, pos=0.0, rpy=0.0, vel=0.0, rate=0.0, first_env: int = 0, enabled: bool = True):
+        """Randomised episode starts (mds_set_episode_randomisation; needs ``set_episodes`` first): a done env's drones restart at their
+        reset position ± ``pos`` (m), initial attitude ± ``rpy`` (rad), world velocity ± ``vel`` (m/s) and body rates ± ``rate`` (rad/s),
+        each a scalar or a 3-vector of half-widths, drawn uniformly by a counter-based generator on the device.  A start is a pure
+        function of (``seed``, the drone's global index ``first_env * D + i``, the env's ``count`` of completed episodes, the number of
+        ``reset_episodes`` calls): it does not depend on ``steps_per_launch`` or on how the envs are sharded -- give every shard the same
+        seed and the global index of its first env.  ``enabled=False`` switches it off; so does ``set_episodes(enabled=False)``."""
+        self._require_open()
+        if not enabled:
+            capi.check(self._lib.mds_set_episode_randomisation(self._h, None, self._stream()), "mds_set_episode_randomisation")
+            return
+        p = capi.MdsEpisodeRandomisation()
+        p.seed, p.first_env = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_env)
+        for name, val in (("pos", pos), ("rpy", rpy), ("vel", vel), ("rate", rate)):
+            setattr(p, name, (C.c_double * 3)(*np.broadcast_to(np.asarray(val, dtype=np.float64), (3,))))
+        capi.check(self._lib.mds_set_episode_randomisation(self._h, C.byref(p), self._stream()), "mds_set_episode_randomisation")
+
+    def reset_episodes(self):
+        """Every drone to a freshly drawn start and every env's running episode restarted (mds_reset_episodes; the completed episodes'
+        statistics stay).  Returns the observation tensor [E,D,20]; it is reused by the next call."""
+        self._require_open()
+        capi.check(self._lib.mds_reset_episodes(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()), "mds_reset_episodes")
+        return self._obs
+
     def set_rollout_streams(self, n_streams: int = 0):
         """How rollout_geometric issues its steps: 0 auto, 1 the current stream only, 2 the two halves of the shard on two
         internal streams (mds_set_rollout_streams).  Same results either way."""
