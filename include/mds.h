@@ -207,6 +207,24 @@ int mds_set_lemniscate(mds_handle* h, const double* params_host, void* stream);
  * mds_set_traj_specialisation(h, 0) keeps a handle on the general kernels (default 1; tests compare the two). */
 int mds_traj_yaw_free(mds_handle* h);
 int mds_set_traj_specialisation(mds_handle* h, int on);
+/* THE PHASE TABLE.  sin / cos of a Lemniscate's phase omega t + phase_shift depend on (omega, phase_shift, t) alone.  Every upload
+ * also compares, as the doubles they are, columns omega and phase_shift of every row i >= 64 with row i - 64: where all are equal
+ * (always for n <= 64; per-slot parameters with num_drones dividing 64; one parameter set for all) the lanes of every wavefront
+ * share their phases and mds_traj_phase_periodic returns 1.  Segment tables clear the flag.  On such a handle that is also yaw-free
+ * the whole-rollout kernel (launch form 2 of mds_rollout_geometric, and mds_rollout_geometric_fused; MDS_F32, Euler, no drag) reads
+ * the pair of each step from a table of the handle's -- 2048 control steps x 64 lanes, 1 MB of device memory, allocated by the first
+ * upload that qualifies (MDS_ENOMEM leaves the handle as it was) -- instead of computing it per drone and step.  A small kernel fills
+ * the rows on the stream of the call that needs them; a call that continues at the time the last one ended reads on behind it.
+ * Contract: the results are the same bits with the table on or off (the fill evaluates the very functions the loop does, its times
+ * formed by the same repeated additions of the control period).  The table belongs to the handle and is ordered by the caller's
+ * stream, as the state is: calls on one handle from two streams need the caller's ordering.  A call that is being captured into a
+ * hipGraph neither reads nor fills the table (what its rows hold is host bookkeeping of eager enqueues, which a replay would outlive):
+ * it computes the phase in the kernel, and a replay does not depend on what the table holds by then.
+ * mds_set_traj_phase_table(h, 0) switches it off (default 1); mds_set_traj_specialisation(h, 0) switches it off as well.
+ * mds_get_last_rollout_phase_table: 1 when the last whole-rollout launch of the handle read the table. */
+int mds_traj_phase_periodic(mds_handle* h);
+int mds_set_traj_phase_table(mds_handle* h, int on);
+int mds_get_last_rollout_phase_table(mds_handle* h);
 int mds_set_geometric_gains(mds_handle* h, const mds_geometric_gains* gains);
 
 /* One fused control step of simulations/EnvGeometric.py:434-469 for every drone:

@@ -142,6 +142,15 @@ struct mds_handle {
   int traj_mode = 0;             // 1: per-drone Lemniscate planes (fused fp32 fast path), 2: general segment tables
   bool traj_yaw_free = false;    // every Lemniscate of the last upload has yaw_rate = +-0 (mds_set_lemniscate; segment tables: false)
   bool traj_spec = true;         // mds_set_traj_specialisation: such a handle steps through the yaw-free kernels
+  // the phase table of the whole-rollout loop (k_rollout_geometric_y0p): sin / cos of the Lemniscate phases, one row of 64 pairs per step
+  bool traj_phase_periodic = false;   // the last upload's (omega, phase_shift) repeat every 64 drones (lemniscate_phase_periodic; segment tables: false)
+  bool phase_tab_on = true;      // mds_set_traj_phase_table
+  void* phase_tab = nullptr;     // T [kPhaseTabRows][64][2], allocated by the first upload that qualifies
+  bool phase_tab_filled = false; // the rows hold the steps of a flight; an upload clears it
+  int phase_tab_rows = 0;        // how many rows the last fill wrote
+  int phase_tab_row = 0;         // the row of the step that follows the last launch served ...
+  double phase_tab_t = 0.0;      // ... and its time: a launch that starts there, to the bit, goes on reading; any other refills from row 0
+  int last_rollout_phase_table = 0;   // the last whole-rollout launch read the table (mds_get_last_rollout_phase_table)
   double* segs = nullptr;        // device [MDS_SEG_DIM, total]: field-major (mds_traj.hpp SegTable)
   int nseg_total = 0;
   int* tinfo = nullptr;          // device [n, 3] = first segment, nseg | compound << 16, stride between pieces (mds_traj.hpp TrajInfo)
@@ -894,6 +903,18 @@ int mds_step(mds_handle* h, const void* action, void* obs, void* stream) {
   return check_launches();
 }
 
+// The phase table (mds_kernels.hip, TAB): kPhaseTabRows control steps of 64 (sin, cos) pairs, 1 MB in fp32, filled by
+// k_lemniscate_phase_table on the stream of the launch that needs rows (phase_table_rows has the policy: a launch that does not
+// continue the last one fills its own rows, a continuing flight doubles its fills up to the whole table, which then serves 40
+// launches of 50 steps).  The whole-rollout loop has the table form where its step is the leanest: fp32
+// arithmetic and storage, Euler, no drag, GeometricControl (launch_rollout_kernel).  RK4, drag, compensated and fp16 storage and float64
+// compute the phase in the kernel: the same bits either way, so which launches read the table is the library's choice.
+constexpr int kPhaseTabRows = 2048;
+static bool phase_table_built(const mds_handle* h) {
+  return h->cfg.dtype == MDS_F32 && h->cfg.integrator != MDS_INTEGRATOR_RK4 && !has_drag(h) && !h->envfx;
+}
+static size_t phase_table_bytes(const mds_handle* h) { return (size_t)kPhaseTabRows * kPhaseLanes * 2 * comp_size(h->cfg.dtype); }
+
 int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   MDS_DEV(h);
   if (!h || !params) return fail(MDS_EINVAL, "mds_set_lemniscate: null argument");
@@ -907,6 +928,14 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
     for (int k = 0; k < 3; ++k) centres[(size_t)3 * i + k] = params[(size_t)7 * i + 2 + k];
     yaw_free = yaw_free && params[(size_t)7 * i + 5] == 0.0;
   }
+  // the lanes of every wave share their phases (mds_traj_phase_periodic): the first upload of that kind on a handle whose whole-rollout
+  // loop has the table form (phase_table_built) gets the table's block -- before anything of the handle changes: out of memory leaves it as it was
+  const bool phase_periodic = lemniscate_phase_periodic(params, n);
+  if (yaw_free && phase_periodic && phase_table_built(h))
+    if (int arc = h->mem.alloc(&h->phase_tab, phase_table_bytes(h))) {
+      delete[] centres;
+      return arc;
+    }
   int rc = mds_set_origin(h, centres, stream);
   delete[] centres;
   if (rc != MDS_OK) return rc;
@@ -920,16 +949,27 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   h->has_traj = true;
   h->traj_mode = 1;
   h->traj_yaw_free = yaw_free;
+  h->traj_phase_periodic = phase_periodic;
+  h->phase_tab_filled = false;           // new phases: the rows are refilled by the next launch that reads them
   return MDS_OK;
 }
 
 int mds_traj_yaw_free(mds_handle* h) { return h && h->traj_yaw_free ? 1 : 0; }
+int mds_traj_phase_periodic(mds_handle* h) { return h && h->traj_phase_periodic ? 1 : 0; }
 
 int mds_set_traj_specialisation(mds_handle* h, int on) {
   if (!h) return fail(MDS_EINVAL, "mds_set_traj_specialisation: null handle");
   h->traj_spec = on != 0;
   return MDS_OK;
 }
+
+int mds_set_traj_phase_table(mds_handle* h, int on) {
+  if (!h) return fail(MDS_EINVAL, "mds_set_traj_phase_table: null handle");
+  h->phase_tab_on = on != 0;
+  return MDS_OK;
+}
+
+int mds_get_last_rollout_phase_table(mds_handle* h) { return h ? h->last_rollout_phase_table : 0; }
 
 // the fused GeometricControl step and the whole-rollout kernel take the yaw-free form together (both launch forms, every dtype)
 static bool use_yaw_free(const mds_handle* h) { return h->traj_mode == 1 && h->traj_yaw_free && h->traj_spec; }
@@ -960,6 +1000,7 @@ int mds_set_trajectory_segments(mds_handle* h, const double* segs, const int32_t
   h->has_traj = true;
   h->traj_mode = 2;
   h->traj_yaw_free = false;
+  h->traj_phase_periodic = false;
   return MDS_OK;
 }
 
@@ -1039,6 +1080,37 @@ int mds_step_geometric(mds_handle* h, double t, void* obs, void* act, void* stre
   return check_launches();
 }
 
+// The table rows of a launch of n_steps control steps from t0 (use_phase_table holds), filled on st where they are not there yet.
+// A launch that starts at the time the last one ended at, to the bit, reads on behind it; when it would run past the rows that are
+// filled, the table is filled from its first step, twice as many rows as the time before up to all 2048 (a flight of many launches: 40
+// of 50 steps per fill).  A launch at any other time -- a caller that passes k * dt, the first call of a flight -- fills its own n_steps
+// rows only: a fill costs its longest chain of dependent additions, and a short call must not pay for 2048 steps it may never fly.
+// (fp32: the handles phase_table_built admits)
+static const float* phase_table_rows(mds_handle* h, double t0, double dt, int n_steps, hipStream_t st) {
+  using T = float;
+  const bool continues = h->phase_tab_filled && memcmp(&t0, &h->phase_tab_t, sizeof(double)) == 0;
+  if (!continues || h->phase_tab_row + n_steps > h->phase_tab_rows) {
+    const int rows = continues ? std::min(kPhaseTabRows, std::max(2 * h->phase_tab_rows, n_steps)) : n_steps;
+    k_lemniscate_phase_table<T><<<grid_for((size_t)rows * kPhaseLanes, 256), 256, 0, st>>>(h->n, h->ld, t0, dt, rows, (const T*)h->lem, (T*)h->phase_tab);
+    h->phase_tab_filled = true;
+    h->phase_tab_rows = rows;
+    h->phase_tab_row = 0;
+  }
+  const T* first = (const T*)h->phase_tab + (size_t)h->phase_tab_row * kPhaseLanes * 2;
+  h->phase_tab_row += n_steps;
+  for (int k = 0; k < n_steps; ++k) t0 += dt;        // (as Chunks::advance and the kernel's loop)
+  h->phase_tab_t = t0;
+  return first;
+}
+// A launch that is being captured into a graph does not read the table: what the rows hold is bookkeeping of the host, true at the
+// moment of an eager enqueue.  A captured launch would bake a pointer to rows that later calls and uploads overwrite before a replay,
+// and a captured fill would mark rows as filled that no kernel has written yet.  Such a launch computes the phase in the kernel (the
+// same bits), from the t0 and the planes baked into it, and leaves the bookkeeping as it found it.
+static bool use_phase_table(const mds_handle* h, int n_steps, hipStream_t st) {
+  return use_yaw_free(h) && h->traj_phase_periodic && h->phase_tab_on && h->phase_tab && n_steps >= 1 && n_steps <= kPhaseTabRows &&
+         !stream_is_capturing(st);
+}
+
 // One launch of the whole-rollout kernel: n_steps control steps with the state in registers.  ctrl: 0 GeometricControl, 1 LQRController
 // (12-state), 2 LQROmegaController + ThrustOmega, 3 LQRYankOmegaController + YankOmega (Lemniscate trajectories only, no fp16 storage:
 // rollout_fused has refused the rest).  Step k's observation goes to obs_log + k * log_stride
@@ -1048,6 +1120,7 @@ static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_step
   const dim3 grid = grid_for(h->n, kBlock);
   const double dt = 1.0 / h->cfg.ctrl_freq;
   const int omode = obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog;
+  h->last_rollout_phase_table = 0;
   auto launch = [&](auto DT, auto CTRL) {
     using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
     constexpr int COMP = DT.COMP ? 1 : 0;
@@ -1063,6 +1136,16 @@ static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_step
                 (T*)rpm_track(h), (S*)obs_log, log_stride, (S*)obs_last, (S*)h->state_lo);
         } else {
           auto* k = &k_rollout_geometric<T, S, RK4(), DRAG(), CTRL(), COMP, OBS()>;
+          // the lean loops of a yaw-free handle whose phases repeat from wave to wave read sin / cos of the phase from the handle's table
+          if constexpr (CTRL() == 0 && std::is_same_v<S, float> && !RK4() && !DRAG() && COMP == 0 && OBS() >= 0)
+            if (use_phase_table(h, n_steps, st)) {
+              const T* rows = (const T*)phase_table_rows(h, t0, dt, n_steps, st);
+              k_rollout_geometric_y0p<T, S, false, false, 0, OBS()><<<grid, kBlock, 0, st>>>(
+                  params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs_log, log_stride,
+                  (S*)obs_last, (T*)h->ll, (const S*)obs_last, (S*)h->state_lo, rows);
+              h->last_rollout_phase_table = 1;
+              return;
+            }
           if constexpr (CTRL() == 0)
             if (use_yaw_free(h)) k = &k_rollout_geometric_y0<T, S, RK4(), DRAG(), COMP, OBS()>;
           k<<<grid, kBlock, 0, st>>>(params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs_log,

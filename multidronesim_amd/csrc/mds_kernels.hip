@@ -808,15 +808,28 @@ constexpr int kObsLast = 0, kObsInPlace = 1, kObsLog = 2;
 template <typename T, bool RK4, bool DRAG, int CTRL, int COMP, int OBS> constexpr int rollout_min_waves() {
   return !(sizeof(T) == 4 && !RK4 && !DRAG && CTRL == 0 && COMP == 0) ? 1 : (OBS == kObsInPlace || OBS == kObsLog) ? 6 : OBS == kObsLast ? 5 : 1;
 }
-// The loop is the body of two entry points: k_rollout_geometric (Y0 false: the general form) and, for CTRL 0, k_rollout_geometric_y0 (the
+// The loop is the body of three entry points: k_rollout_geometric (Y0 false: the general form) and, for CTRL 0, k_rollout_geometric_y0 (the
 // yaw-free form of the trajectory and the controller, mds_math.hpp: what the library launches for a handle whose Lemniscates all have
-// yaw_rate = 0).  c_arg must be the kernel's first argument (the lean loops read the constants through the kernarg segment).
-template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP, int OBS, bool Y0>
+// yaw_rate = 0) and k_rollout_geometric_y0p (the yaw-free form with the phase table, TAB below).  c_arg must be the kernel's first
+// argument (the lean loops read the constants through the kernarg segment).
+//
+// TAB (k_rollout_geometric_y0p, yaw-free handles whose phases repeat from wave to wave: mds_traj_phase_periodic): sin / cos of the
+// Lemniscate phase are not computed in the loop.  Step k reads its pair from row k of phase_tab -- 64 x (s, c) per row, the row of
+// the launch's first step first (k_lemniscate_phase_table) -- at lane (drone & 63); the loop then forms no time and has no float64
+// instruction.  The load of step k + 1's pair is issued in step k, behind the last use of step k's (the last step re-reads its own
+// row): a step's worth of arithmetic hides it, also where a SIMD holds one wave.
+template <typename T> struct alignas(2 * sizeof(T)) PhaseSC {
+  T s, c;
+};
+constexpr int kPhaseLanes = kWave;      // one table row: the phases of drones 0 .. 63 (of drone n - 1 behind the last)
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP, int OBS, bool Y0, bool TAB = false>
 __device__ __forceinline__ void rollout_geometric_body(
     unsigned char* lds, const Consts<T>& c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt,
     const int n_steps, S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log,
-    const size_t log_stride, S* __restrict__ obs_last, T* __restrict__ ll, const S* __restrict__ obs_prev, S* __restrict__ state_lo) {
+    const size_t log_stride, S* __restrict__ obs_last, T* __restrict__ ll, const S* __restrict__ obs_prev, S* __restrict__ state_lo,
+    const T* __restrict__ phase_tab = nullptr) {
   static_assert(!Y0 || CTRL == 0, "the yaw-free form is GeometricControl's");
+  static_assert(!TAB || Y0, "the phase table serves the yaw-free form");
   const bool comp = COMP < 0 ? state_lo != nullptr : COMP != 0;
   const int omode = OBS < 0 ? (obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog) : OBS;
   // re-forming the loop's invariants per step pays where the register budget decides (Euler, plain storage: fp32 125 -> 71 VGPRs,
@@ -853,6 +866,27 @@ __device__ __forceinline__ void rollout_geometric_body(
   // re-form what derives from them per step; the others hoist what they like, from scalar bases now)
   ObsRowOffs row_offs = obs_row_offs<S, true>(i, threadIdx.x);
   ObsRowOffs* const ro = OBS != kObsLast ? &row_offs : nullptr;
+  // TAB: the lane's place in a row, formed once; the row is a wave-uniform pointer that advances with the steps
+  // (a byte offset in one VGPR, re-read per step so that the load keeps its scalar-base + 32-bit-offset form; phase_tab has a row even
+  // for a launch of no steps)
+  const unsigned tab_off = ((unsigned)il & (unsigned)(kPhaseLanes - 1)) * (unsigned)sizeof(PhaseSC<T>);
+  const unsigned char* tab_row = reinterpret_cast<const unsigned char*>(phase_tab);
+  auto tab_load = [&]() {
+    unsigned off = tab_off;
+    MDS_KEEP_V(off);
+    return *reinterpret_cast<const PhaseSC<T>*>(tab_row + off);
+  };
+  PhaseSC<T> sc = {T(0), T(1)};
+  if (TAB) {
+    // the first pair, and the state and the parameters loaded above, are waited for here, ahead of the loop: a loaded value whose first
+    // use is inside the loop gets its wait there, and in every later step that wait sits out the row stores of the step before
+    sc = tab_load();
+    MDS_KEEP_V(sc.s);
+    MDS_KEEP_V(sc.c);
+    for (T* v : {&in.P.a, &in.P.omega, &in.P.cx, &in.P.cy, &in.P.cz, &in.s.p.x, &in.s.p.y, &in.s.p.z, &in.s.q[0], &in.s.q[1], &in.s.q[2], &in.s.q[3],
+                 &in.s.v.x, &in.s.v.y, &in.s.v.z, &in.s.w.x, &in.s.w.y, &in.s.w.z})
+      MDS_KEEP_V(*v);
+  }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     const bool last = k == n_steps - 1;
@@ -872,7 +906,12 @@ __device__ __forceinline__ void rollout_geometric_body(
         MDS_KEEP_V(in.P.a);
         if (!Y0) MDS_KEEP_V(in.P.yaw_rate);
       }
-      const Desired<T> des = lemniscate_local<T, Y0>(in.P, t);
+      // (TAB is the yaw-free form: it does not read t, and the loop does not advance it)
+      const Desired<T> des = TAB ? lemniscate_from_sc<T, Y0>(in.P, sc.s, sc.c, t) : lemniscate_local<T, Y0>(in.P, t);
+      if (TAB) {               // the next step's pair, into the registers this step's has just left: on its way while the step computes
+        tab_row += last ? 0 : kPhaseLanes * sizeof(PhaseSC<T>);
+        sc = tab_load();
+      }
       T u[4];
       if (CTRL == 0) {
         if (!kCarry) {
@@ -907,6 +946,14 @@ __device__ __forceinline__ void rollout_geometric_body(
     } else if (want) {
       pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
     }
+    if (TAB) {
+      // the next pair is waited for HERE, ahead of this step's row stores.  The wait counts every vector-memory operation in flight
+      // (loads and stores share one counter): here those are the load, a step's arithmetic old, and the stores of the step before, long
+      // acknowledged.  Left to its first use at the top of the next step the wait would also sit out the stores issued just now --
+      // measured: the whole gain at full size, and +7 % where a SIMD holds one wave.
+      MDS_KEEP_V(sc.s);
+      MDS_KEEP_V(sc.c);
+    }
     // the clipped RPM leaves with the last step (not carried to the end of the loop)
     if (valid && last && (DRAG || last_rpm)) {
       unsigned iu = (unsigned)i;
@@ -916,7 +963,7 @@ __device__ __forceinline__ void rollout_geometric_body(
     if (omode == kObsInPlace) write_obs_rows<S, T, true, kLean>(lds, obs_log, n, i, valid, o, ro);       // the same rows rewritten every step: keep them cached
     else if (omode == kObsLog) write_obs_rows<S, T, false, kLean>(lds, obs_log + (size_t)k * log_stride, n, i, valid, o, ro);
     if (omode != kObsInPlace && obs_last != nullptr && last) write_obs_rows<S, T, false, kLean>(lds, obs_last, n, i, valid, o, ro);
-    t = uniform_f64(t + ctrl_dt);
+    if (!TAB) t = uniform_f64(t + ctrl_dt);
   }
   if (valid) {
     store_state<S, T>(state, ld, i, in.s);
@@ -944,6 +991,36 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, 0, COMP, O
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
   rollout_geometric_body<T, S, RK4, DRAG, 0, COMP, OBS, true>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm, obs_log,
                                                               log_stride, obs_last, ll, obs_prev, state_lo);
+}
+
+// The yaw-free loop with the phase table (TAB above): the same arguments plus the table row of the launch's first step.  The row
+// after it belongs to the second step, and so on: the caller provides n_steps rows.
+template <typename T, typename S, bool RK4, bool DRAG, int COMP = -1, int OBS = -1>
+__global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, 0, COMP, OBS>())) void k_rollout_geometric_y0p(
+    const Consts<T> c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt, const int n_steps,
+    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
+    S* __restrict__ obs_last, T* __restrict__ ll, const S* __restrict__ obs_prev, S* __restrict__ state_lo, const T* __restrict__ phase_tab) {
+  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  rollout_geometric_body<T, S, RK4, DRAG, 0, COMP, OBS, true, true>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm, obs_log,
+                                                                    log_stride, obs_last, ll, obs_prev, state_lo, phase_tab);
+}
+
+// Fills the phase table: row k, lane l = sin / cos of the phase of drone min(l, n - 1) at the time of step k, the values
+// lemniscate_local forms in the loop -- m_sincos(reduced_phase<T>(t_k, omega, phase_shift)), t_k = t0 after k additions of ctrl_dt in
+// double, as the step loop and the host's Chunks advance it (never t0 + k * ctrl_dt).  One thread per entry, blocks of 256 = 4 rows.
+template <typename T>
+__global__ __launch_bounds__(256) void k_lemniscate_phase_table(const int n, const size_t ld, const double t0, const double ctrl_dt,
+                                                                const int n_rows, const T* __restrict__ lem, T* __restrict__ phase_tab) {
+  const int e = blockIdx.x * 256 + threadIdx.x, k = e / kPhaseLanes, l = e % kPhaseLanes;
+  if (n <= 0 || k >= n_rows) return;
+  const size_t i = (size_t)min(l, n - 1);
+  const T omega = lem[4 * i + 1], phase_shift = lem[4 * i + 3];      // (the planes as load_geo_in reads them)
+  double t = t0;
+#pragma unroll 8
+  for (int j = 0; j < k; ++j) t = t + ctrl_dt;     // (the kernel's run time: the last row's chain of dependent additions)
+  PhaseSC<T> sc;
+  m_sincos(reduced_phase<T>(t, omega, phase_shift), &sc.s, &sc.c);
+  reinterpret_cast<PhaseSC<T>*>(phase_tab)[e] = sc;
 }
 
 // The same whole-rollout loop for general trajectories (segment tables, evaluated in double every step like k_step_traj).

@@ -799,11 +799,14 @@ template <typename T> struct LemniscateParams {
 };
 // Y0 (yaw-free form): for a trajectory uploaded with yaw_rate = +-0 -- the library decides per handle, mds_set_lemniscate -- the yaw
 // block is not formed: yaw = yaw_rate = +0, what the general form returns there up to the sign of yaw_rate's zero.
-template <typename T, bool Y0 = false> MDS_HD Desired<T> lemniscate_local(const LemniscateParams<T>& P, double t) {
+//
+// The function in two parts.  (s, c) = sin / cos of the phase omega t + phase_shift depend on (omega, phase_shift, t) alone, and both
+// m_sincos(float) and reduced_phase<float> are written in explicit fma: the pair has the same bits wherever it is computed.
+// lemniscate_from_sc is everything behind it; a caller that has the pair from elsewhere (the whole-rollout loop reads it from the
+// handle's phase table, k_lemniscate_phase_table) calls it directly.  t is read by the general form's yaw block only, and has no
+// default: a caller of the general form cannot leave it out.
+template <typename T, bool Y0 = false> MDS_HD Desired<T> lemniscate_from_sc(const LemniscateParams<T>& P, T s, T c, double t) {
   Desired<T> d;
-  const T th = reduced_phase<T>(t, P.omega, P.phase_shift);
-  T s, c;
-  m_sincos(th, &s, &c);
   const T s2 = s * s, c2 = c * c;
   const T den = T(1) + s2;
   const T inv = m_rcp(den);
@@ -829,6 +832,20 @@ template <typename T, bool Y0 = false> MDS_HD Desired<T> lemniscate_local(const 
   d.yaw = T(3.14159265358979323846) * sy;
   d.yaw_rate = T(3.14159265358979323846) * P.yaw_rate * cy;
   return d;
+}
+template <typename T, bool Y0 = false> MDS_HD Desired<T> lemniscate_local(const LemniscateParams<T>& P, double t) {
+  T s, c;
+  m_sincos(reduced_phase<T>(t, P.omega, P.phase_shift), &s, &c);
+  return lemniscate_from_sc<T, Y0>(P, s, c, t);
+}
+
+// The rule under which the lanes of every wave share their phases (mds_set_lemniscate decides it per upload): params is [n, 7] as
+// uploaded, and for every row i >= 64 columns 1 (omega) and 6 (phase_shift) equal those of row i - 64, compared as the doubles they are.
+// Drone i then has the phase of drone i & 63.  Trivially true for n <= 64.  Host code.
+inline bool lemniscate_phase_periodic(const double* params, long n) {
+  for (long i = 64; i < n; ++i)
+    if (params[7 * i + 1] != params[7 * (i - 64) + 1] || params[7 * i + 6] != params[7 * (i - 64) + 6]) return false;
+  return true;
 }
 
 // ------------------------------------------------------------------------------------

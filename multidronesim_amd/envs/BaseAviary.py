@@ -592,6 +592,22 @@ class BaseAviary:
         self._require_open()
         capi.check(self._lib.mds_set_traj_specialisation(self._h, C.c_int(1 if on else 0)), "mds_set_traj_specialisation")
 
+    def traj_phase_periodic(self) -> bool:
+        """True when ``omega`` and ``phase_shift`` of the last ``set_trajectories`` repeat every 64 drones (mds_traj_phase_periodic): on a
+        yaw-free env the whole-rollout kernel then reads sin / cos of the phase from the env's table (the same bits as computing them)."""
+        self._require_open()
+        return bool(self._lib.mds_traj_phase_periodic(self._h))
+
+    def set_traj_phase_table(self, on: bool = True):
+        """``False`` keeps the whole-rollout kernel computing the phase per drone and step (mds_set_traj_phase_table; default on)."""
+        self._require_open()
+        capi.check(self._lib.mds_set_traj_phase_table(self._h, C.c_int(1 if on else 0)), "mds_set_traj_phase_table")
+
+    def last_rollout_phase_table(self) -> bool:
+        """Whether the last whole-rollout launch read the phase table (mds_get_last_rollout_phase_table)."""
+        self._require_open()
+        return bool(self._lib.mds_get_last_rollout_phase_table(self._h))
+
     def rollout_form_for(self, n_steps: int) -> int:
         self._require_open()
         return int(self._lib.mds_rollout_form_for(self._h, C.c_int(int(n_steps))))
