@@ -221,10 +221,22 @@ int mds_set_traj_specialisation(mds_handle* h, int on);
  * hipGraph neither reads nor fills the table (what its rows hold is host bookkeeping of eager enqueues, which a replay would outlive):
  * it computes the phase in the kernel, and a replay does not depend on what the table holds by then.
  * mds_set_traj_phase_table(h, 0) switches it off (default 1); mds_set_traj_specialisation(h, 0) switches it off as well.
- * mds_get_last_rollout_phase_table: 1 when the last whole-rollout launch of the handle read the table. */
+ * mds_get_last_rollout_phase_table: 1 when the last whole-rollout launch of the handle read the table (in either of its two forms).
+ *
+ * THE DESIRED-STATE TABLE.  Where column a repeats every 64 drones as well (mds_traj_desired_periodic; every script of the reference
+ * leaves a at its default), everything the yaw-free controller reads of the desired state in the local frame -- it depends on
+ * (a, omega, sin, cos) alone, the centre is the frame's origin -- is the same in lane l of every wavefront.  The table's block then
+ * has rows of 64 lanes x 8 values (4 MB for the 2048 steps, in place of the 1 MB; MDS_ENOMEM leaves the handle as it was) and the loop
+ * reads those instead of the pair: same fill policy, same times, same contract (the same bits on or off), same rule for captured calls.
+ * A handle whose phases repeat but whose a does not keeps the pair's table.  mds_set_traj_desired_table(h, 0) falls back to the pair's
+ * table (default 1); mds_set_traj_phase_table(h, 0) and mds_set_traj_specialisation(h, 0) switch both off.
+ * mds_get_last_rollout_desired_table: 1 when the last whole-rollout launch read the wide rows. */
 int mds_traj_phase_periodic(mds_handle* h);
 int mds_set_traj_phase_table(mds_handle* h, int on);
 int mds_get_last_rollout_phase_table(mds_handle* h);
+int mds_traj_desired_periodic(mds_handle* h);
+int mds_set_traj_desired_table(mds_handle* h, int on);
+int mds_get_last_rollout_desired_table(mds_handle* h);
 int mds_set_geometric_gains(mds_handle* h, const mds_geometric_gains* gains);
 
 /* One fused control step of simulations/EnvGeometric.py:434-469 for every drone:

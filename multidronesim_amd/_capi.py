@@ -90,6 +90,9 @@ PROTOTYPES = {
     "mds_traj_phase_periodic": (C.c_int, [_P]),
     "mds_set_traj_phase_table": (C.c_int, [_P, C.c_int]),
     "mds_get_last_rollout_phase_table": (C.c_int, [_P]),
+    "mds_traj_desired_periodic": (C.c_int, [_P]),
+    "mds_set_traj_desired_table": (C.c_int, [_P, C.c_int]),
+    "mds_get_last_rollout_desired_table": (C.c_int, [_P]),
     "mds_set_trajectory_segments": (C.c_int, [_P, _PD, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _PD, C.c_int32, _P]),
     "mds_traj_eval": (C.c_int, [_P, C.c_double, _P, _P]),
     "mds_set_geometric_gains": (C.c_int, [_P, C.POINTER(MdsGeometricGains)]),

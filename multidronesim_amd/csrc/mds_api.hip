@@ -145,12 +145,18 @@ struct mds_handle {
   // the phase table of the whole-rollout loop (k_rollout_geometric_y0p): sin / cos of the Lemniscate phases, one row of 64 pairs per step
   bool traj_phase_periodic = false;   // the last upload's (omega, phase_shift) repeat every 64 drones (lemniscate_phase_periodic; segment tables: false)
   bool phase_tab_on = true;      // mds_set_traj_phase_table
-  void* phase_tab = nullptr;     // T [kPhaseTabRows][64][2], allocated by the first upload that qualifies
+  void* phase_tab = nullptr;     // T [kPhaseTabRows][64][2] (pairs) or [kPhaseTabRows][2][64][4] (wide rows), allocated by the first upload that qualifies
   bool phase_tab_filled = false; // the rows hold the steps of a flight; an upload clears it
   int phase_tab_rows = 0;        // how many rows the last fill wrote
   int phase_tab_row = 0;         // the row of the step that follows the last launch served ...
   double phase_tab_t = 0.0;      // ... and its time: a launch that starts there, to the bit, goes on reading; any other refills from row 0
   int last_rollout_phase_table = 0;   // the last whole-rollout launch read the table (mds_get_last_rollout_phase_table)
+  // the desired-state table (k_rollout_geometric_y0d): the same block and bookkeeping, rows of 64 x 8 values (LemDesired8)
+  bool traj_desired_periodic = false; // the last upload's a repeats every 64 drones as well (lemniscate_desired_periodic; segment tables: false)
+  bool desired_tab_on = true;         // mds_set_traj_desired_table
+  size_t phase_tab_bytes = 0;         // the size of the block: narrow rows (1 MB) or wide ones (4 MB, serves either layout)
+  bool phase_tab_wide = false;        // the layout of the rows the last fill wrote
+  int last_rollout_desired_table = 0; // ... and it read wide rows (mds_get_last_rollout_desired_table)
   double* segs = nullptr;        // device [MDS_SEG_DIM, total]: field-major (mds_traj.hpp SegTable)
   int nseg_total = 0;
   int* tinfo = nullptr;          // device [n, 3] = first segment, nseg | compound << 16, stride between pieces (mds_traj.hpp TrajInfo)
@@ -909,11 +915,14 @@ int mds_step(mds_handle* h, const void* action, void* obs, void* stream) {
 // launches of 50 steps).  The whole-rollout loop has the table form where its step is the leanest: fp32
 // arithmetic and storage, Euler, no drag, GeometricControl (launch_rollout_kernel).  RK4, drag, compensated and fp16 storage and float64
 // compute the phase in the kernel: the same bits either way, so which launches read the table is the library's choice.
+// Where the amplitudes repeat as well (lemniscate_desired_periodic) the block is 4 MB and its rows hold the eight values the controller
+// reads of the desired state (LemDesired8) instead of the pair: same fills, same bookkeeping, k_rollout_geometric_y0d.
 constexpr int kPhaseTabRows = 2048;
 static bool phase_table_built(const mds_handle* h) {
   return h->cfg.dtype == MDS_F32 && h->cfg.integrator != MDS_INTEGRATOR_RK4 && !has_drag(h) && !h->envfx;
 }
-static size_t phase_table_bytes(const mds_handle* h) { return (size_t)kPhaseTabRows * kPhaseLanes * 2 * comp_size(h->cfg.dtype); }
+// (wide: rows of 64 x 8 values, the desired-state table; a block of that size serves the narrow rows too)
+static size_t phase_table_bytes(const mds_handle* h, bool wide) { return (size_t)kPhaseTabRows * kPhaseLanes * (wide ? 8 : 2) * comp_size(h->cfg.dtype); }
 
 int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   MDS_DEV(h);
@@ -930,12 +939,21 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   }
   // the lanes of every wave share their phases (mds_traj_phase_periodic): the first upload of that kind on a handle whose whole-rollout
   // loop has the table form (phase_table_built) gets the table's block -- before anything of the handle changes: out of memory leaves it as it was
-  const bool phase_periodic = lemniscate_phase_periodic(params, n);
-  if (yaw_free && phase_periodic && phase_table_built(h))
-    if (int arc = h->mem.alloc(&h->phase_tab, phase_table_bytes(h))) {
-      delete[] centres;
-      return arc;
+  // An upload whose amplitudes repeat as well (mds_traj_desired_periodic) gets the block of the wide rows, in place of a narrow one
+  // an earlier upload may have left: the new block first, then the old one freed.
+  const bool phase_periodic = lemniscate_phase_periodic(params, n), desired_periodic = lemniscate_desired_periodic(params, n);
+  if (yaw_free && phase_periodic && phase_table_built(h)) {
+    const size_t want = phase_table_bytes(h, desired_periodic);
+    if (h->phase_tab_bytes < want) {
+      const int arc = h->phase_tab ? h->mem.replace(&h->phase_tab, want, [](void*) { return 0; }) : h->mem.alloc(&h->phase_tab, want);
+      if (arc) {
+        delete[] centres;
+        return arc;
+      }
+      h->phase_tab_bytes = want;
+      h->phase_tab_filled = false;
     }
+  }
   int rc = mds_set_origin(h, centres, stream);
   delete[] centres;
   if (rc != MDS_OK) return rc;
@@ -950,12 +968,14 @@ int mds_set_lemniscate(mds_handle* h, const double* params, void* stream) {
   h->traj_mode = 1;
   h->traj_yaw_free = yaw_free;
   h->traj_phase_periodic = phase_periodic;
+  h->traj_desired_periodic = desired_periodic;
   h->phase_tab_filled = false;           // new phases: the rows are refilled by the next launch that reads them
   return MDS_OK;
 }
 
 int mds_traj_yaw_free(mds_handle* h) { return h && h->traj_yaw_free ? 1 : 0; }
 int mds_traj_phase_periodic(mds_handle* h) { return h && h->traj_phase_periodic ? 1 : 0; }
+int mds_traj_desired_periodic(mds_handle* h) { return h && h->traj_desired_periodic ? 1 : 0; }
 
 int mds_set_traj_specialisation(mds_handle* h, int on) {
   if (!h) return fail(MDS_EINVAL, "mds_set_traj_specialisation: null handle");
@@ -969,7 +989,14 @@ int mds_set_traj_phase_table(mds_handle* h, int on) {
   return MDS_OK;
 }
 
+int mds_set_traj_desired_table(mds_handle* h, int on) {
+  if (!h) return fail(MDS_EINVAL, "mds_set_traj_desired_table: null handle");
+  h->desired_tab_on = on != 0;
+  return MDS_OK;
+}
+
 int mds_get_last_rollout_phase_table(mds_handle* h) { return h ? h->last_rollout_phase_table : 0; }
+int mds_get_last_rollout_desired_table(mds_handle* h) { return h ? h->last_rollout_desired_table : 0; }
 
 // the fused GeometricControl step and the whole-rollout kernel take the yaw-free form together (both launch forms, every dtype)
 static bool use_yaw_free(const mds_handle* h) { return h->traj_mode == 1 && h->traj_yaw_free && h->traj_spec; }
@@ -1001,6 +1028,7 @@ int mds_set_trajectory_segments(mds_handle* h, const double* segs, const int32_t
   h->traj_mode = 2;
   h->traj_yaw_free = false;
   h->traj_phase_periodic = false;
+  h->traj_desired_periodic = false;
   return MDS_OK;
 }
 
@@ -1086,17 +1114,20 @@ int mds_step_geometric(mds_handle* h, double t, void* obs, void* act, void* stre
 // of 50 steps per fill).  A launch at any other time -- a caller that passes k * dt, the first call of a flight -- fills its own n_steps
 // rows only: a fill costs its longest chain of dependent additions, and a short call must not pay for 2048 steps it may never fly.
 // (fp32: the handles phase_table_built admits)
-static const float* phase_table_rows(mds_handle* h, double t0, double dt, int n_steps, hipStream_t st) {
+// wide: rows of the desired-state table (use_desired_table holds); rows of the other layout count as not filled.
+static const float* phase_table_rows(mds_handle* h, double t0, double dt, int n_steps, bool wide, hipStream_t st) {
   using T = float;
-  const bool continues = h->phase_tab_filled && memcmp(&t0, &h->phase_tab_t, sizeof(double)) == 0;
+  const bool continues = h->phase_tab_filled && h->phase_tab_wide == wide && memcmp(&t0, &h->phase_tab_t, sizeof(double)) == 0;
   if (!continues || h->phase_tab_row + n_steps > h->phase_tab_rows) {
     const int rows = continues ? std::min(kPhaseTabRows, std::max(2 * h->phase_tab_rows, n_steps)) : n_steps;
-    k_lemniscate_phase_table<T><<<grid_for((size_t)rows * kPhaseLanes, 256), 256, 0, st>>>(h->n, h->ld, t0, dt, rows, (const T*)h->lem, (T*)h->phase_tab);
+    auto* const fill = wide ? &k_lemniscate_phase_table<T, true> : &k_lemniscate_phase_table<T, false>;
+    fill<<<grid_for((size_t)rows * kPhaseLanes, 256), 256, 0, st>>>(h->n, h->ld, t0, dt, rows, (const T*)h->lem, (T*)h->phase_tab);
     h->phase_tab_filled = true;
+    h->phase_tab_wide = wide;
     h->phase_tab_rows = rows;
     h->phase_tab_row = 0;
   }
-  const T* first = (const T*)h->phase_tab + (size_t)h->phase_tab_row * kPhaseLanes * 2;
+  const T* first = (const T*)h->phase_tab + (size_t)h->phase_tab_row * kPhaseLanes * (wide ? 8 : 2);
   h->phase_tab_row += n_steps;
   for (int k = 0; k < n_steps; ++k) t0 += dt;        // (as Chunks::advance and the kernel's loop)
   h->phase_tab_t = t0;
@@ -1110,6 +1141,10 @@ static bool use_phase_table(const mds_handle* h, int n_steps, hipStream_t st) {
   return use_yaw_free(h) && h->traj_phase_periodic && h->phase_tab_on && h->phase_tab && n_steps >= 1 && n_steps <= kPhaseTabRows &&
          !stream_is_capturing(st);
 }
+// ... and the wide rows where the amplitudes repeat too, the block has their size and mds_set_traj_desired_table has not switched them off
+static bool use_desired_table(const mds_handle* h, int n_steps, hipStream_t st) {
+  return use_phase_table(h, n_steps, st) && h->traj_desired_periodic && h->desired_tab_on && h->phase_tab_bytes >= phase_table_bytes(h, true);
+}
 
 // One launch of the whole-rollout kernel: n_steps control steps with the state in registers.  ctrl: 0 GeometricControl, 1 LQRController
 // (12-state), 2 LQROmegaController + ThrustOmega, 3 LQRYankOmegaController + YankOmega (Lemniscate trajectories only, no fp16 storage:
@@ -1120,7 +1155,7 @@ static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_step
   const dim3 grid = grid_for(h->n, kBlock);
   const double dt = 1.0 / h->cfg.ctrl_freq;
   const int omode = obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog;
-  h->last_rollout_phase_table = 0;
+  h->last_rollout_phase_table = h->last_rollout_desired_table = 0;
   auto launch = [&](auto DT, auto CTRL) {
     using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
     constexpr int COMP = DT.COMP ? 1 : 0;
@@ -1139,11 +1174,14 @@ static void launch_rollout_kernel(mds_handle* h, int ctrl, double t0, int n_step
           // the lean loops of a yaw-free handle whose phases repeat from wave to wave read sin / cos of the phase from the handle's table
           if constexpr (CTRL() == 0 && std::is_same_v<S, float> && !RK4() && !DRAG() && COMP == 0 && OBS() >= 0)
             if (use_phase_table(h, n_steps, st)) {
-              const T* rows = (const T*)phase_table_rows(h, t0, dt, n_steps, st);
-              k_rollout_geometric_y0p<T, S, false, false, 0, OBS()><<<grid, kBlock, 0, st>>>(
-                  params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h), (S*)obs_log, log_stride,
-                  (S*)obs_last, (T*)h->ll, (const S*)obs_last, (S*)h->state_lo, rows);
+              // ... or, where the amplitudes repeat as well, what the controller reads of the desired state
+              const bool wide = use_desired_table(h, n_steps, st);
+              const T* rows = (const T*)phase_table_rows(h, t0, dt, n_steps, wide, st);
+              auto* const kt = wide ? &k_rollout_geometric_y0d<T, S, false, false, 0, OBS()> : &k_rollout_geometric_y0p<T, S, false, false, 0, OBS()>;
+              kt<<<grid, kBlock, 0, st>>>(params<T>(h).c, gain, h->n, h->ld, t0, dt, n_steps, (S*)h->state, (const T*)h->lem, (T*)rpm_track(h),
+                                          (S*)obs_log, log_stride, (S*)obs_last, (T*)h->ll, (const S*)obs_last, (S*)h->state_lo, rows);
               h->last_rollout_phase_table = 1;
+              h->last_rollout_desired_table = wide ? 1 : 0;
               return;
             }
           if constexpr (CTRL() == 0)

@@ -818,11 +818,17 @@ template <typename T, bool RK4, bool DRAG, int CTRL, int COMP, int OBS> constexp
 // the launch's first step first (k_lemniscate_phase_table) -- at lane (drone & 63); the loop then forms no time and has no float64
 // instruction.  The load of step k + 1's pair is issued in step k, behind the last use of step k's (the last step re-reads its own
 // row): a step's worth of arithmetic hides it, also where a SIMD holds one wave.
+//
+// TAB 2 (k_rollout_geometric_y0d, handles whose amplitudes repeat as well: mds_traj_desired_periodic): the table holds what the controller
+// reads of the desired state (LemDesired8, mds_math.hpp) instead of the pair.  A row is 64 x 16 bytes (inv, mx, my, inv3) followed by
+// 64 x 16 bytes (vx, vy, Xx, Xy): two 16-byte loads per lane and step, each contiguous across the wave.  The loop then has no a, no
+// omega and no reciprocal for the trajectory; the prefetch and its wait are those of TAB 1.
 template <typename T> struct alignas(2 * sizeof(T)) PhaseSC {
   T s, c;
 };
 constexpr int kPhaseLanes = kWave;      // one table row: the phases of drones 0 .. 63 (of drone n - 1 behind the last)
-template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP, int OBS, bool Y0, bool TAB = false>
+constexpr int kTabNone = 0, kTabPhase = 1, kTabDesired = 2;
+template <typename T, typename S, bool RK4, bool DRAG, int CTRL, int COMP, int OBS, bool Y0, int TAB = kTabNone>
 __device__ __forceinline__ void rollout_geometric_body(
     unsigned char* lds, const Consts<T>& c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt,
     const int n_steps, S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log,
@@ -830,6 +836,7 @@ __device__ __forceinline__ void rollout_geometric_body(
     const T* __restrict__ phase_tab = nullptr) {
   static_assert(!Y0 || CTRL == 0, "the yaw-free form is GeometricControl's");
   static_assert(!TAB || Y0, "the phase table serves the yaw-free form");
+  static_assert(TAB != kTabDesired || (CTRL == 0 && sizeof(T) == 4), "the desired-state table serves the fp32 GeometricControl loop");
   const bool comp = COMP < 0 ? state_lo != nullptr : COMP != 0;
   const int omode = OBS < 0 ? (obs_log == nullptr ? kObsLast : log_stride == 0 ? kObsInPlace : kObsLog) : OBS;
   // re-forming the loop's invariants per step pays where the register budget decides (Euler, plain storage: fp32 125 -> 71 VGPRs,
@@ -876,8 +883,34 @@ __device__ __forceinline__ void rollout_geometric_body(
     MDS_KEEP_V(off);
     return *reinterpret_cast<const PhaseSC<T>*>(tab_row + off);
   };
+  // TAB 2: the lane's two 16-byte groups of a row, kPhaseLanes * 16 bytes apart.  `off` comes out of an asm that names what the step
+  // has formed from the row it holds: the loads cannot be issued ahead of those, so the next row lands in the registers this one has left
+  // (issued any earlier it needs eight registers of its own and eight copies at the bottom of the step).
+  const unsigned tab8_off = ((unsigned)il & (unsigned)(kPhaseLanes - 1)) * (unsigned)sizeof(Quad<T>);
+  // (the two groups are carried as the 16-byte registers they are loaded into: held as eight scalars they get copies at the wait)
+  typedef T Row4 __attribute__((vector_size(4 * sizeof(T))));
+  Row4 row_a = {}, row_b = {};
+  auto tab8_load = [&](unsigned off) {
+    row_a = *reinterpret_cast<const Row4*>(tab_row + off);
+    row_b = *reinterpret_cast<const Row4*>(tab_row + off + kPhaseLanes * sizeof(Quad<T>));
+  };
+  // one statement for the two: one wait for both loads
+  auto tab8_keep = [&]() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(row_a), "+v"(row_b));
+#endif
+  };
   PhaseSC<T> sc = {T(0), T(1)};
-  if (TAB) {
+  if (TAB == kTabDesired) {
+    // (as below: the first row, the state and the centres are waited for ahead of the loop; a and omega are not read at all)
+    unsigned off = tab8_off;
+    MDS_KEEP_V(off);
+    tab8_load(off);
+    tab8_keep();
+    for (T* v : {&in.P.cx, &in.P.cy, &in.P.cz, &in.s.p.x, &in.s.p.y, &in.s.p.z, &in.s.q[0], &in.s.q[1], &in.s.q[2], &in.s.q[3],
+                 &in.s.v.x, &in.s.v.y, &in.s.v.z, &in.s.w.x, &in.s.w.y, &in.s.w.z})
+      MDS_KEEP_V(*v);
+  } else if (TAB) {
     // the first pair, and the state and the parameters loaded above, are waited for here, ahead of the loop: a loaded value whose first
     // use is inside the loop gets its wait there, and in every later step that wait sits out the row stores of the step before
     sc = tab_load();
@@ -901,6 +934,31 @@ __device__ __forceinline__ void rollout_geometric_body(
 #endif
     T act[4], clipped[4];
     {
+      if constexpr (TAB == kTabDesired) {
+        // The step's share of the desired state, from the row it holds: p_rel, R^T v_d and the x, y of the controller's tw are the
+        // last uses of the eight values (desired8_*, mds_math.hpp: the operations the other forms of this loop execute there).
+        if (kCarry) {
+          MDS_KEEP_V(F.r22m1);
+          F.R.m[8] = T(1) + F.r22m1;
+        } else {
+          F = make_frame(in.s.q, in.s.w);
+        }
+        const LemDesired8<T> d8 = {row_a[0], row_a[1], row_a[2], row_a[3], row_b[0], row_b[1], row_b[2], row_b[3]};
+        GeoPre<T> pre;
+        const V3<T> p_rel = desired8_p_rel(d8, in.s.p);
+        desired8_pre(d8, c.kp[0], c.kp[1], p_rel, F.R, pre);
+        // the next step's row, into the registers this step's has just left: on its way while the step computes
+        tab_row += last ? 0 : kPhaseLanes * sizeof(LemDesired8<T>);
+        unsigned off = tab8_off;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(off) : "v"(pre.RTvd.x), "v"(pre.RTvd.y), "v"(pre.RTvd.z), "v"(pre.tw_x), "v"(pre.tw_y), "v"(p_rel.x), "v"(p_rel.y));
+#endif
+        tab8_load(off);
+        Desired<T> des = {};     // (not read: the yaw-free controller takes what it needs of it from pre)
+        T u[4];
+        geometric_control<T, true, true>(c, p_rel, F.R, in.s.v, F.av, des, u, nullptr, &pre);
+        input_to_action(c, u, act);
+      } else {
       // (per-lane parameters: what lemniscate_local derives from them is formed here every step, not held across the loop)
       if (kLean) {
         MDS_KEEP_V(in.P.a);
@@ -933,6 +991,7 @@ __device__ __forceinline__ void rollout_geometric_body(
       if (CTRL <= 1) input_to_action(c, u, act);
       else if (CTRL == 2) thrust_omega_control(c, (T)ctrl_dt, u, in.s.w, L, act);
       else yank_omega_control(c, (T)ctrl_dt, u, thr, in.s.w, L, act);
+      }
     }
     // (compensated storage and RK4 form their own thrust direction: there the frame serves the controller and the row only)
     if (comp) aviary_step_comp<T, RK4, DRAG>(c, in.s, in.r, act, prev, clipped);
@@ -946,7 +1005,9 @@ __device__ __forceinline__ void rollout_geometric_body(
     } else if (want) {
       pack_obs(in.s, V3<T>{in.P.cx, in.P.cy, in.P.cz}, clipped, o);
     }
-    if (TAB) {
+    if (TAB == kTabDesired) {
+      tab8_keep();             // (the wait of the next row: placed as the pair's, below)
+    } else if (TAB) {
       // the next pair is waited for HERE, ahead of this step's row stores.  The wait counts every vector-memory operation in flight
       // (loads and stores share one counter): here those are the load, a step's arithmetic old, and the stores of the step before, long
       // acknowledged.  Left to its first use at the top of the next step the wait would also sit out the stores issued just now --
@@ -1001,26 +1062,45 @@ __global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, 0, COMP, O
     S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
     S* __restrict__ obs_last, T* __restrict__ ll, const S* __restrict__ obs_prev, S* __restrict__ state_lo, const T* __restrict__ phase_tab) {
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
-  rollout_geometric_body<T, S, RK4, DRAG, 0, COMP, OBS, true, true>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm, obs_log,
-                                                                    log_stride, obs_last, ll, obs_prev, state_lo, phase_tab);
+  rollout_geometric_body<T, S, RK4, DRAG, 0, COMP, OBS, true, kTabPhase>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm,
+                                                                         obs_log, log_stride, obs_last, ll, obs_prev, state_lo, phase_tab);
+}
+// The yaw-free loop with the desired-state table (TAB 2 above): the same arguments; desired_tab is the wide row of the launch's first step.
+template <typename T, typename S, bool RK4, bool DRAG, int COMP = -1, int OBS = -1>
+__global__ __launch_bounds__(kBlock, (rollout_min_waves<T, RK4, DRAG, 0, COMP, OBS>())) void k_rollout_geometric_y0d(
+    const Consts<T> c_arg, const void* __restrict__ Kp, const int n, const size_t ld, double t, const double ctrl_dt, const int n_steps,
+    S* __restrict__ state, const T* __restrict__ lem, T* __restrict__ last_rpm, S* __restrict__ obs_log, const size_t log_stride,
+    S* __restrict__ obs_last, T* __restrict__ ll, const S* __restrict__ obs_prev, S* __restrict__ state_lo, const T* __restrict__ desired_tab) {
+  __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
+  rollout_geometric_body<T, S, RK4, DRAG, 0, COMP, OBS, true, kTabDesired>(lds, c_arg, Kp, n, ld, t, ctrl_dt, n_steps, state, lem, last_rpm,
+                                                                           obs_log, log_stride, obs_last, ll, obs_prev, state_lo, desired_tab);
 }
 
 // Fills the phase table: row k, lane l = sin / cos of the phase of drone min(l, n - 1) at the time of step k, the values
 // lemniscate_local forms in the loop -- m_sincos(reduced_phase<T>(t_k, omega, phase_shift)), t_k = t0 after k additions of ctrl_dt in
 // double, as the step loop and the host's Chunks advance it (never t0 + k * ctrl_dt).  One thread per entry, blocks of 256 = 4 rows.
-template <typename T>
+// WIDE: the rows of the desired-state table instead -- lemniscate_desired8 of the same pair and the drone's a, in the row layout of TAB 2.
+template <typename T, bool WIDE = false>
 __global__ __launch_bounds__(256) void k_lemniscate_phase_table(const int n, const size_t ld, const double t0, const double ctrl_dt,
                                                                 const int n_rows, const T* __restrict__ lem, T* __restrict__ phase_tab) {
   const int e = blockIdx.x * 256 + threadIdx.x, k = e / kPhaseLanes, l = e % kPhaseLanes;
   if (n <= 0 || k >= n_rows) return;
   const size_t i = (size_t)min(l, n - 1);
   const T omega = lem[4 * i + 1], phase_shift = lem[4 * i + 3];      // (the planes as load_geo_in reads them)
-  double t = t0;
-#pragma unroll 8
-  for (int j = 0; j < k; ++j) t = t + ctrl_dt;     // (the kernel's run time: the last row's chain of dependent additions)
+  const double t = lemniscate_table_time(t0, ctrl_dt, k);      // (the kernel's run time: the last row's chain of dependent additions)
   PhaseSC<T> sc;
   m_sincos(reduced_phase<T>(t, omega, phase_shift), &sc.s, &sc.c);
-  reinterpret_cast<PhaseSC<T>*>(phase_tab)[e] = sc;
+  if constexpr (WIDE) {
+    LemniscateParams<T> P = {};
+    P.a = lem[4 * i];
+    P.omega = omega;
+    const LemDesired8<T> d = lemniscate_desired8(P, sc.s, sc.c);
+    Quad<T>* const row = reinterpret_cast<Quad<T>*>(phase_tab) + (size_t)k * (2 * kPhaseLanes);
+    row[l] = {{d.inv, d.mx, d.my, d.inv3}};
+    row[kPhaseLanes + l] = {{d.vx, d.vy, d.Xx, d.Xy}};
+  } else {
+    reinterpret_cast<PhaseSC<T>*>(phase_tab)[e] = sc;
+  }
 }
 
 // The same whole-rollout loop for general trajectories (segment tables, evaluated in double every step like k_step_traj).

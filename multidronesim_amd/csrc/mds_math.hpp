@@ -44,8 +44,21 @@ MDS_HD float m_rsqrt(float x) { return 1.0f / sqrtf(x); }
 MDS_HD double m_rcp(double x) { return 1.0 / x; }
 MDS_HD double m_sqrt(double x) { return sqrt(x); }
 MDS_HD double m_rsqrt(double x) { return 1.0 / sqrt(x); }
+// MDS_HOST_UNFUSED_FMA (host builds of the tests only): m_fma rounds its product, so that a form written in explicit fma can be compared,
+// operation by operation, with the same expression in plain operators compiled without contraction (tests/desired_table_main.cpp).
+#if defined(MDS_HOST_UNFUSED_FMA) && !defined(__HIPCC__)
+MDS_HD float m_fma(float a, float b, float c) {
+  volatile float ab = a * b;
+  return ab + c;
+}
+MDS_HD double m_fma(double a, double b, double c) {
+  volatile double ab = a * b;
+  return ab + c;
+}
+#else
 MDS_HD float m_fma(float a, float b, float c) { return fmaf(a, b, c); }
 MDS_HD double m_fma(double a, double b, double c) { return fma(a, b, c); }
+#endif
 // a * b rounded on its own, for a product that feeds a plain sum and must not be contracted into it (the yaw-free controller form: the
 // general form rounds these products first, inside a cross product whose other term is a literal zero).  The product goes through an
 // empty asm the optimiser cannot look through: switching contraction off for the multiplication alone is not enough, a negation
@@ -839,6 +852,59 @@ template <typename T, bool Y0 = false> MDS_HD Desired<T> lemniscate_local(const 
   return lemniscate_from_sc<T, Y0>(P, s, c, t);
 }
 
+// The yaw-free desired state of the whole-rollout loop in two parts, for a caller that takes the first from a table (the handle's
+// desired-state table, k_lemniscate_phase_table<T, true>; mds_traj_desired_periodic).  Everything lemniscate_from_sc<T, true> derives
+// from (a, omega, s, c) reads nothing of the drone's state; what the controller reads of it is eight values:
+//   inv = 1 / (1 + s^2), mx = c (s a), my = c a      des.p = inv (mx, my): the controller's p_rel is fma(-inv, m, p)
+//   vx, vy                                            des.v, rounded: multipliers of the three R^T v_d rows
+//   inv3 = -inv^3 / 8, Xx, Xy                         des.a = inv3 (Xx, Xy): the controller's tw is fma(inv3, X, -(Kp p_rel))
+// The cut is where the fp32 yaw-free loop (k_rollout_geometric_y0p) rounds a value on its own: the last multiply of des.p and of des.a
+// is contracted into its consumer there, so the table holds the factors and the loop keeps that fma.  Both sides are written in explicit
+// m_fma / m_mul_rn, operation by operation what that loop executes: the fill is another kernel, and the compiler gets no contraction
+// decision of its own in it.  The operations, their operands and their association are those of lemniscate_from_sc and of
+// geometric_control<T, true>'s p_rel and tw (tests/test_desired_table_cpu.py compares the two with every product rounded).
+template <typename T> struct alignas(4 * sizeof(T)) Quad {
+  T v[4];
+};
+template <typename T> struct LemDesired8 {
+  T inv, mx, my, inv3;     // the table's first 16 bytes of a lane
+  T vx, vy, Xx, Xy;        // the second
+};
+template <typename T> MDS_HD LemDesired8<T> lemniscate_desired8(const LemniscateParams<T>& P, T s, T c) {
+  LemDesired8<T> d;
+  d.inv = m_rcp(m_fma(s, s, T(1)));
+  const T s2 = s * s, c2 = c * c;                  // (operands of fma and of products only)
+  const T poly = m_fma(c2, m_fma(s, s, T(-1)), m_fma(s2, s2, s2));
+  const T aw = P.a * P.omega, naw = -aw;
+  const T q = T(1) + m_fma(T(2), c2, s2);
+  const T inv2 = d.inv * d.inv;
+  d.vx = inv2 * (poly * naw);
+  d.vy = inv2 * (q * (s * naw));
+  const T sin2 = m_mul_rn(c, s + s);               // (2 s) c: read by a sum below
+  const T cos2 = m_fma(c, c, -s2), cos4 = m_fma(-sin2, sin2 + sin2, T(1));
+  const T aw2 = aw * P.omega;
+  d.mx = c * (s * P.a);
+  d.my = c * P.a;
+  d.inv3 = T(-0.125) * (d.inv * inv2);
+  d.Xx = m_fma(cos2, T(3), T(7)) * (sin2 * (T(4) * aw2));
+  d.Xy = (m_fma(T(44), cos2, cos4) + T(-21)) * (c * aw2);
+  return d;
+}
+// ... and behind the cut: p - des.p (des.p.z = 0), and the x and y of geometric_control<T, true>'s tw = des.a - Kp p_rel
+template <typename T> MDS_HD V3<T> desired8_p_rel(const LemDesired8<T>& d, V3<T> p) {
+  return {m_fma(-d.inv, d.mx, p.x), m_fma(-d.inv, d.my, p.y), p.z};
+}
+// (GeoPre, below: what geometric_control<T, true> takes ready-made; R^T v_d is its RTvd, operation by operation)
+template <typename T> struct GeoPre {
+  V3<T> RTvd;
+  T tw_x, tw_y;
+};
+template <typename T> MDS_HD void desired8_pre(const LemDesired8<T>& d, T kp_x, T kp_y, V3<T> p_rel, const M3<T>& R, GeoPre<T>& pre) {
+  pre.RTvd = {m_fma(R.m[0], d.vx, R.m[3] * d.vy), m_fma(R.m[1], d.vx, R.m[4] * d.vy), m_fma(R.m[2], d.vx, R.m[5] * d.vy)};
+  pre.tw_x = m_fma(d.inv3, d.Xx, -(kp_x * p_rel.x));
+  pre.tw_y = m_fma(d.inv3, d.Xy, -(kp_y * p_rel.y));
+}
+
 // The rule under which the lanes of every wave share their phases (mds_set_lemniscate decides it per upload): params is [n, 7] as
 // uploaded, and for every row i >= 64 columns 1 (omega) and 6 (phase_shift) equal those of row i - 64, compared as the doubles they are.
 // Drone i then has the phase of drone i & 63.  Trivially true for n <= 64.  Host code.
@@ -846,6 +912,21 @@ inline bool lemniscate_phase_periodic(const double* params, long n) {
   for (long i = 64; i < n; ++i)
     if (params[7 * i + 1] != params[7 * (i - 64) + 1] || params[7 * i + 6] != params[7 * (i - 64) + 6]) return false;
   return true;
+}
+// The time of row k of the handle's table: k additions of the control period to the launch's t0 in double, as the step loop and the
+// host's chunks advance it -- never t0 + k * ctrl_dt, which rounds once where the loop rounds k times.
+MDS_HD double lemniscate_table_time(double t0, double ctrl_dt, int k) {
+  double t = t0;
+#pragma unroll 8
+  for (int j = 0; j < k; ++j) t = t + ctrl_dt;
+  return t;
+}
+// ... and their whole desired state in the local frame: the amplitude (column 0) repeats as well.  (a, omega, s, c) is all
+// lemniscate_desired8 reads -- the centre is the frame's origin and never enters.  Trivially true for n <= 64.  Host code.
+inline bool lemniscate_desired_periodic(const double* params, long n) {
+  for (long i = 64; i < n; ++i)
+    if (params[7 * i] != params[7 * (i - 64)]) return false;
+  return lemniscate_phase_periodic(params, n);
 }
 
 // ------------------------------------------------------------------------------------
@@ -892,20 +973,28 @@ template <typename T> struct GeoAux {  // return_omegas=True outputs (:106-108)
 // yaw_rate = +-0, and the same bits unless a sum that lost a zero term is itself exactly zero (x*0 + (-0) is +0, -0 alone is not);
 // where the state is not finite the general form returns NaN throughout (x*0 is NaN for x = inf), this one may not.  DESIGN.md section 4
 // has the argument term by term.
-template <typename T, bool Y0 = false>
+//
+// PRE (with Y0): R^T v_d and the x, y of tw come ready-made in *pre -- from the row of the handle's desired-state table, desired8_pre --
+// and des is not read.
+template <typename T, bool Y0 = false, bool PRE = false>
 MDS_HD void geometric_control(const Consts<T>& c, V3<T> p_rel, const M3<T>& R, V3<T> v_world, V3<T> w,
-                              const Desired<T>& des, T u[4], GeoAux<T>* aux) {
+                              const Desired<T>& des, T u[4], GeoAux<T>* aux, const GeoPre<T>* pre = nullptr) {
+  static_assert(!PRE || Y0, "the ready-made terms are the yaw-free form's");
   const V3<T> Kp = {c.kp[0], c.kp[1], c.kp[2]}, Kv = {c.kv[0], c.kv[1], c.kv[2]};
   const V3<T> v_b = mulT(R, v_world);                                   // :70
   V3<T> RTvd, tw;
-  if (Y0) {                                                             // des.v.z = 0: the third product of each row is not formed
+  if constexpr (PRE) {
+    RTvd = pre->RTvd;
+  } else if (Y0) {                                                      // des.v.z = 0: the third product of each row is not formed
     RTvd = {m_fma(R.m[0], des.v.x, R.m[3] * des.v.y), m_fma(R.m[1], des.v.x, R.m[4] * des.v.y), m_fma(R.m[2], des.v.x, R.m[5] * des.v.y)};
   } else {
     RTvd = mulT(R, des.v);
   }
   const V3<T> ev = v_b - RTvd;
   // f_des_body/m = R^T(g e3 - Kp ep + a_d) - Kv ev - w x R^T v_d      (:73-74)
-  if (Y0) {                                                             // des.a.z = 0: (0 - x) + g = g - x, x rounded first
+  if constexpr (PRE) {
+    tw = {pre->tw_x, pre->tw_y, c.g_ctrl - m_mul_rn(Kp.z, p_rel.z)};
+  } else if (Y0) {                                                      // des.a.z = 0: (0 - x) + g = g - x, x rounded first
     tw = {des.a.x - Kp.x * p_rel.x, des.a.y - Kp.y * p_rel.y, c.g_ctrl - m_mul_rn(Kp.z, p_rel.z)};
   } else {
     tw = des.a - hadamard(Kp, p_rel);

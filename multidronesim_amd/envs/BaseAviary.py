@@ -608,6 +608,22 @@ class BaseAviary:
         self._require_open()
         return bool(self._lib.mds_get_last_rollout_phase_table(self._h))
 
+    def traj_desired_periodic(self) -> bool:
+        """True when ``a`` repeats every 64 drones as well as ``omega`` and ``phase_shift`` (mds_traj_desired_periodic): the env's table then
+        holds what the controller reads of the desired state, not only sin / cos of the phase (the same bits as computing it)."""
+        self._require_open()
+        return bool(self._lib.mds_traj_desired_periodic(self._h))
+
+    def set_traj_desired_table(self, on: bool = True):
+        """``False`` falls back to the table of sin / cos pairs (mds_set_traj_desired_table; default on)."""
+        self._require_open()
+        capi.check(self._lib.mds_set_traj_desired_table(self._h, C.c_int(1 if on else 0)), "mds_set_traj_desired_table")
+
+    def last_rollout_desired_table(self) -> bool:
+        """Whether the last whole-rollout launch read the desired-state rows (mds_get_last_rollout_desired_table)."""
+        self._require_open()
+        return bool(self._lib.mds_get_last_rollout_desired_table(self._h))
+
     def rollout_form_for(self, n_steps: int) -> int:
         self._require_open()
         return int(self._lib.mds_rollout_form_for(self._h, C.c_int(int(n_steps))))
