@@ -369,6 +369,41 @@ int mds_set_episode_randomisation(mds_handle* h, const mds_episode_randomisation
  * obs_dev [n,20] unless NULL (MDS_EALIGN as for mds_get_obs).  MDS_ESTATE when randomisation is not configured.  Only enqueues. */
 int mds_reset_episodes(mds_handle* h, void* obs_dev, void* stream);
 
+/* AN MLP POLICY INSIDE THE EPISODE ROLLOUT KERNEL (the arithmetic, stated once: multidronesim_amd/csrc/mds_policy.hpp).  The shape
+ * of stable-baselines3's MlpPolicy actor on gym-pybullet-drones' kinematic observation and ActionType.RPM: 12 features per drone
+ * (position - target | roll, pitch, yaw | world velocity | world angular velocity), n_hidden hidden layers of `width` neurons with
+ * tanh or relu, a linear output of 4, and rpm[j] = rpm_base + rpm_scale * clamp(y[j], -1, 1), which then goes through the step like
+ * any commanded RPM (the motor clip stays where it is).  weights_host: the policy's policy_n_weights doubles packed as torch packs
+ * an nn.Sequential of Linear layers: weight [out][in] row-major, then bias, layer after layer.  An input normaliser folds into
+ * layer 1 on the host (mds_policy.hpp says how).  Each drone acts on its own state only. */
+typedef struct mds_episode_policy {
+  int32_t n_hidden;             /* 1 or 2 */
+  int32_t width;                /* 1..64 */
+  int32_t activation;           /* 0 tanh, 1 relu */
+  int32_t reserved;
+  double rpm_base, rpm_scale;   /* NaN: hover_rpm, 0.05 * hover_rpm */
+} mds_episode_policy;
+/* Configures (params NULL: switches off) the policy: converts the weights to the compute type, zero-padded to the width the device
+ * code is built for (32 or 64: a padded neuron changes no bit), into device memory the handle owns.  MDS_EINVAL for a field out of
+ * range, a weight that is not finite, an rpm_base or rpm_scale that is infinite; MDS_EUNSUPPORTED wherever mds_set_episodes is, and
+ * for MDS_F16 storage (fp16 storage needs a storage-faithful oracle of the policy loop first); MDS_ESTATE without mds_set_episodes.
+ * mds_set_episodes(h, NULL, ..) switches the policy off too; a re-configuration of the episode parameters, the collision causes or
+ * the randomisation keeps it.  A failed call leaves the handle as it was.  No other entry point reads the policy: every one of them
+ * gives on a handle with a policy the bits it gives without.  Set-up path: synchronous. */
+int mds_set_episode_policy(mds_handle* h, const mds_episode_policy* params, const double* weights_host, void* stream);
+/* The policy alone, on caller-supplied observation rows obs_dev [n,20] -> rpm_dev [n,4] (storage type; MDS_EALIGN as for
+ * mds_get_obs): the position feature is obs[0:3] - (target + origin), both in the world frame.  With mds_step_episodes this is the
+ * policy-in-the-loop form of mds_rollout_episodes_policy.  MDS_ESTATE without a policy.  Only enqueues. */
+int mds_episode_policy_compute(mds_handle* h, const void* obs_dev, void* rpm_dev, void* stream);
+/* mds_rollout_episodes' loop with the table read replaced by the policy: at every step each drone acts on its current state (the
+ * post-reset state where its env was just done, the loaded state at the first step of a call).  Slot j % log_slots of action_log_dev
+ * [log_slots, n, 4] (storage type) receives the commanded RPM of step j = first_step + k; every other ring, log_slots and obs_dev
+ * mean what they mean in mds_rollout_episodes.  Collision causes and randomised starts are honoured when configured, with the same
+ * ordinal / generation rule: the draws do not depend on who supplies the actions.  steps_per_launch changes no bit.  MDS_ESTATE
+ * without a policy.  Only enqueues, on the caller's stream. */
+int mds_rollout_episodes_policy(mds_handle* h, int first_step, int n_steps, void* obs_log_dev, int log_slots, void* action_log_dev,
+                                void* reward_log_dev, int32_t* flags_log_dev, int steps_per_launch, void* obs_dev, void* stream);
+
 /* How mds_rollout_geometric / mds_rollout_step / mds_rollout_cbf_geometric issue their steps.  Drones never read each
  * other's rows in the fused step (and a barrier row couples drones of one env only), so the two halves of the shard are
  * independent step chains: on two internal streams one half's load/store bursts fill the other's compute phase, and the

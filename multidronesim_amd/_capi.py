@@ -57,6 +57,14 @@ class MdsEpisodeRandomisation(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_env", C.c_int64)] + [(k, C.c_double * 3) for k in ("pos", "rpy", "vel", "rate")]
 
 
+class MdsEpisodePolicy(C.Structure):
+    _fields_ = [("n_hidden", C.c_int32), ("width", C.c_int32), ("activation", C.c_int32), ("reserved", C.c_int32),
+                ("rpm_base", C.c_double), ("rpm_scale", C.c_double)]
+
+
+POLICY_IN, POLICY_OUT, POLICY_MAX_WIDTH = 12, 4, 64
+
+
 class MdsError(RuntimeError):
     def __init__(self, status, where, detail):
         super().__init__(f"{where}: {detail} (mds_status {status})")
@@ -116,6 +124,9 @@ PROTOTYPES = {
     "mds_episode_safety_ptrs": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "mds_set_episode_randomisation": (C.c_int, [_P, C.POINTER(MdsEpisodeRandomisation), _P]),
     "mds_reset_episodes": (C.c_int, [_P, _P, _P]),
+    "mds_set_episode_policy": (C.c_int, [_P, C.POINTER(MdsEpisodePolicy), _PD, _P]),
+    "mds_episode_policy_compute": (C.c_int, [_P, _P, _P, _P]),
+    "mds_rollout_episodes_policy": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
     "mds_rollout_geometric_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
     "mds_lemniscate_eval": (C.c_int, [_P, C.c_double, _P, _P]),
     "mds_geometric_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),

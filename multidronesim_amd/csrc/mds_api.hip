@@ -21,6 +21,7 @@
 #endif
 #if MDS_PART & 1
 #include "mds_episode_kernels.hip"  // per-env episodes inside the rollout kernel (part 1 only)
+#include "mds_episode_policy_kernels.hip"   // ... driven by an MLP policy evaluated in the kernel (part 1 only)
 #endif
 #if MDS_PART & 2
 #include "mds_cbf_kernels.hip"      // (part 2 only: it defines a non-template kernel)
@@ -238,6 +239,12 @@ struct mds_handle {
   bool ep_random = false;
   mds_episode_randomisation ep_rand = {};
   uint32_t ep_generation = 0;
+  // the MLP policy of the episodes (mds_set_episode_policy): the parameters with the defaults resolved, and the weights in the compute
+  // type, zero-padded to ep_policy_width (one of kPolicyWidths)
+  bool ep_policy = false;
+  mds_episode_policy ep_pol = {};
+  int ep_policy_width = 0;
+  void* ep_policy_w = nullptr;
 };
 
 template <typename T> static inline const HostParams<T>& params(const mds_handle* h) {
@@ -485,6 +492,15 @@ template <typename T> static EpisodeRandomArgs<T> episode_random_args(const mds_
                          p.rpy, p.vel, p.rate, a.set);
   a.rpy0 = h->init_pose + (size_t)3 * h->n;
   return a;
+}
+// the handle's policy as the kernels take it
+template <typename T> static EpisodePolicy<T> episode_policy_args(const mds_handle* h) {
+  return {(const T*)h->ep_policy_w, h->ep_pol.n_hidden, h->ep_pol.activation, (T)h->ep_pol.rpm_base, (T)h->ep_pol.rpm_scale};
+}
+// the two dtypes the policy kernels are built for (mds_set_episode_policy has refused the others)
+template <typename F> static void with_policy_dtype(int dtype, F&& f) {
+  if (dtype == MDS_F64) f(DType<double, double>{});
+  else f(DType<float, float>{});
 }
 #endif
 
@@ -1319,7 +1335,7 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_set_episodes: null handle");
   if (!p) {
-    h->ep_on = h->ep_safe = h->ep_random = false;
+    h->ep_on = h->ep_safe = h->ep_random = h->ep_policy = false;
     return MDS_OK;
   }
   if (p->max_steps < 0 || !(p->reward_r0 == p->reward_r0) || !(p->term_penalty == p->term_penalty))
@@ -1493,6 +1509,121 @@ int mds_rollout_episodes(mds_handle* h, const void* actions, int n_action_sets, 
 int mds_step_episodes(mds_handle* h, const void* action, void* obs, void* final_obs, void* reward, int32_t* flags, void* stream) {
   if (!h || !action) return fail(MDS_EINVAL, "mds_step_episodes: null argument");
   return mds_rollout_episodes(h, action, 1, 0, 1, final_obs, 1, reward, flags, 1, obs, stream);
+}
+
+// ---- an MLP policy inside the episode rollout kernel (mds_policy.hpp, mds_episode_policy_kernels.hip) ----
+static_assert(sizeof(mds_episode_policy) == 32, "include/mds.h mds_episode_policy: four int32 and two doubles");
+
+int mds_set_episode_policy(mds_handle* h, const mds_episode_policy* p, const double* weights_host, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_set_episode_policy: null handle");
+  if (!p) {
+    h->ep_policy = false;
+    return MDS_OK;
+  }
+  auto finite = [](double x) { return x > -(double)INFINITY && x < (double)INFINITY; };
+  auto finite_or_nan = [&](double x) { return !(x == x) || finite(x); };
+  if (p->n_hidden < 1 || p->n_hidden > 2 || p->width < 1 || p->width > kPolicyMaxWidth || p->activation < 0 || p->activation > 1 || !weights_host ||
+      !finite_or_nan(p->rpm_base) || !finite_or_nan(p->rpm_scale))
+    return fail(MDS_EINVAL, "mds_set_episode_policy: n_hidden in 1..2, width in 1..64, activation 0 or 1, weights, rpm_base / rpm_scale finite or NaN");
+  const int nw = policy_n_weights(p->n_hidden, p->width);
+  for (int k = 0; k < nw; ++k)
+    if (!finite(weights_host[k])) return fail(MDS_EINVAL, "mds_set_episode_policy: a weight is not finite");
+  if (h->cfg.dtype == MDS_F32C || h->cfg.dtype == MDS_F16 || h->envfx || h->cfg.num_drones > kBlock / 2)
+    return fail(MDS_EUNSUPPORTED, "mds_set_episode_policy: built for MDS_F32 / MDS_F64, DYN / DYN_DRAG physics and at most 128 drones per env");
+  if (!h->ep_on) return fail(MDS_ESTATE, "mds_set_episode_policy: no episodes configured (mds_set_episodes)");
+  hipStream_t st = (hipStream_t)stream;
+  // the padded weights in the compute type, built on the host; the new block is filled before the old one is given up (DevMem::replace),
+  // and the handle's settings change only after that
+  // (float64 with the RK4 integrator has no 32-wide rollout kernel, see mds_rollout_episodes_policy: the 64-wide one serves, same bits)
+  const bool wide_only = h->cfg.dtype == MDS_F64 && h->cfg.integrator == MDS_INTEGRATOR_RK4;
+  const int W = wide_only ? kPolicyWidths[1] : policy_device_width(p->width), nw_pad = policy_n_weights(p->n_hidden, W);
+  const size_t cs = comp_size(h->cfg.dtype);
+  std::vector<double> padded((size_t)nw_pad), w64((size_t)nw_pad);
+  std::vector<float> w32(cs == 4 ? (size_t)nw_pad : 0);
+  policy_pad(weights_host, p->n_hidden, p->width, W, padded.data());
+  policy_device_layout(padded.data(), p->n_hidden, W, w64.data());
+  for (size_t k = 0; k < w32.size(); ++k) w32[k] = (float)w64[k];
+  for (size_t k = 0; k < w32.size(); ++k)
+    if (!finite((double)w32[k])) return fail(MDS_EINVAL, "mds_set_episode_policy: a weight is not finite in float32");
+  const void* src = cs == 4 ? (const void*)w32.data() : (const void*)w64.data();
+  MDS_HIP(hipStreamSynchronize(st));          // (set-up path: nothing enqueued may still read the old block)
+  if (int rc = h->mem.replace(&h->ep_policy_w, (size_t)nw_pad * cs, [&](void* fresh) {
+        return dev_status(hipMemcpy(fresh, src, (size_t)nw_pad * cs, hipMemcpyHostToDevice), "mds_set_episode_policy: upload");
+      }))
+    return rc;
+  h->ep_pol = *p;
+  h->ep_pol.reserved = 0;
+  const double hover = sqrt(h->cfg.G * h->cfg.M / (4.0 * h->cfg.KF));
+  if (!(p->rpm_base == p->rpm_base)) h->ep_pol.rpm_base = hover;
+  if (!(p->rpm_scale == p->rpm_scale)) h->ep_pol.rpm_scale = 0.05 * hover;
+  h->ep_policy_width = W;
+  h->ep_policy = true;
+  return MDS_OK;
+}
+
+int mds_episode_policy_compute(mds_handle* h, const void* obs, void* rpm, void* stream) {
+  MDS_DEV(h);
+  if (!h || !obs || !rpm) return fail(MDS_EINVAL, "mds_episode_policy_compute: null argument");
+  if (!aligned16(obs) || !aligned16(rpm)) return fail(MDS_EALIGN, "mds_episode_policy_compute: obs_dev/rpm_dev");
+  if (!h->ep_on || !h->ep_policy) return fail(MDS_ESTATE, "mds_episode_policy_compute: no policy configured (mds_set_episode_policy)");
+  hipStream_t st = (hipStream_t)stream;
+  with_policy_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    with_int<32, 64>(h->ep_policy_width, [&](auto W) {
+      k_episode_policy_compute<T, S, W()><<<grid_for(h->n, kBlock), kBlock, 0, st>>>(h->n, h->ld, (const T*)h->origin, (const T*)h->ep_target,
+                                                                                     episode_policy_args<T>(h), (const S*)obs, (S*)rpm);
+    });
+  });
+  return check_launches();
+}
+
+int mds_rollout_episodes_policy(mds_handle* h, int first_step, int n_steps, void* obs_log, int log_slots, void* action_log, void* reward_log,
+                                int32_t* flags_log, int steps_per_launch, void* obs, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_rollout_episodes_policy: null handle");
+  const bool ring = obs_log || action_log || reward_log || flags_log;
+  if (steps_per_launch < 1 || first_step < 0 || n_steps < 0 || (ring && log_slots < 1)) return fail(MDS_EINVAL, "mds_rollout_episodes_policy: arguments");
+  if (!aligned16(obs) || !aligned16(obs_log) || !aligned16(action_log) || !aligned16(reward_log) || !aligned16(flags_log))
+    return fail(MDS_EALIGN, "mds_rollout_episodes_policy: obs_dev/obs_log_dev/action_log_dev/reward_log_dev/flags_log_dev");
+  if (!h->ep_on || !h->ep_policy) return fail(MDS_ESTATE, "mds_rollout_episodes_policy: no policy configured (mds_set_episodes, mds_set_episode_policy)");
+  hipStream_t st = (hipStream_t)stream;
+  const int D = h->cfg.num_drones, epb = episode_envs_per_block(D);
+  const dim3 grid((unsigned)((h->cfg.num_envs + epb - 1) / epb));
+  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
+  const mds_episode_params& p = h->ep;
+  for (Chunks c{n_steps, steps_per_launch, 0.0, 0.0, ring ? first_step % log_slots : 0, ring ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
+    const int ks = c.len(), s0 = c.slot;
+    const bool last = c.k + ks == n_steps;
+    with_flags([&](auto RK4, auto DRAG) {
+      with_policy_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+        EpisodeRule<T> rule;
+        fill_episode_rule<T>(p.max_steps, p.z_min, p.z_max, p.max_dist, p.max_tilt, p.max_speed, p.max_rate, p.reward_r0, p.term_penalty, rule);
+        char* cb = (char*)h->ep_counters;
+        const size_t sl = h->ep_slots * 8;
+        const EpisodeCounters<T> cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
+        EpisodeRandomArgs<T> rnd = {};
+        if (h->ep_random) rnd = episode_random_args<T>(h);
+        EpisodeSafetyArgs<T> safe = {};
+        if (h->ep_safe) {
+          fill_episode_safety<T>(h->ep_safety.safety_radius, h->ep_safety.zscale, h->ep_safety.n_obs, h->ep_obstacles, safe.set);
+          safe.h_min_step = (T*)h->ep_hmin;
+          safe.h_min_episode = (T*)((char*)h->ep_hmin + sl);
+        }
+        with_int<32, 64>(h->ep_policy_width, [&](auto W) {
+          // not built: float64, RK4, 32 wide -- the one combination whose register allocation leaves a (never accessed) slot in the private
+          // segment; mds_set_episode_policy pads such a handle's policy to 64, which changes no bit
+          if constexpr (!(RK4() && sizeof(T) == 8 && W() == 32))
+          k_rollout_episodes_policy<T, S, RK4(), DRAG(), W()><<<grid, kBlock, 0, st>>>(
+              params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
+              (T*)rpm_track(h), episode_policy_args<T>(h), (S*)action_log, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks,
+              (S*)(last ? obs : nullptr), cnt, h->ep_safe ? 1 : 0, safe, h->ep_random ? 1 : 0, rnd);
+        });
+      });
+    }, rk4, drag);
+  }
+  return check_launches();
 }
 
 int mds_set_rollout_streams(mds_handle* h, int n_streams) {

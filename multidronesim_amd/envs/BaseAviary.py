@@ -558,6 +558,103 @@ class BaseAviary:
         capi.check(self._lib.mds_reset_episodes(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()), "mds_reset_episodes")
         return self._obs
 
+    # ------------------------------------------------------------------ an MLP policy inside the episode rollout kernel
+    def set_episode_policy(self, weights, n_hidden: int, width: int, activation: str = "tanh", rpm_base=None, rpm_scale=None,
+                           enabled: bool = True):
+        """An MLP policy evaluated inside the episode rollout kernel (mds_set_episode_policy; needs ``set_episodes`` first): 12 features
+        per drone (position - target | roll, pitch, yaw | world velocity | world angular velocity), ``n_hidden`` (1 or 2) hidden layers
+        of ``width`` (1..64) neurons with ``activation`` ``"tanh"`` or ``"relu"``, a linear output of 4, and
+        ``rpm = rpm_base + rpm_scale * clamp(y, -1, 1)`` (defaults: ``HOVER_RPM`` and ``0.05 HOVER_RPM``).  ``weights``: the flat
+        vector ``torch.cat([p.detach().flatten() for p in net.parameters()])`` of an ``nn.Sequential`` of ``Linear`` layers (tensor or
+        array).  ``enabled=False`` switches it off; so does ``set_episodes(enabled=False)``."""
+        self._require_open()
+        if not enabled:
+            capi.check(self._lib.mds_set_episode_policy(self._h, None, None, self._stream()), "mds_set_episode_policy")
+            return
+        acts = {"tanh": 0, "relu": 1}
+        if activation not in acts:
+            raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+        n_hidden, width = int(n_hidden), int(width)
+        if n_hidden not in (1, 2) or not 1 <= width <= capi.POLICY_MAX_WIDTH:
+            raise ValueError(f"n_hidden must be 1 or 2 and width in 1..{capi.POLICY_MAX_WIDTH}, got {n_hidden} and {width}")
+        if isinstance(weights, torch.Tensor):
+            weights = weights.detach().double().cpu().numpy()
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        want = (capi.POLICY_IN + 1) * width + (n_hidden - 1) * (width + 1) * width + (width + 1) * capi.POLICY_OUT
+        if w.size != want:
+            raise ValueError(f"a policy of {n_hidden} hidden layer(s) of width {width} has {want} weights, got {w.size}")
+        p = capi.MdsEpisodePolicy(n_hidden, width, acts[activation], 0, float("nan") if rpm_base is None else float(rpm_base),
+                                  float("nan") if rpm_scale is None else float(rpm_scale))
+        capi.check(self._lib.mds_set_episode_policy(self._h, C.byref(p), capi.as_double_ptr(w), self._stream()), "mds_set_episode_policy")
+
+    @staticmethod
+    def _episode_policy_from_torch(module):
+        """``(weights float64 [n], n_hidden, width, activation)`` of an ``nn.Sequential`` of the supported shape: ``Linear(12, w)``, act,
+        [``Linear(w, w)``, the same act,] ``Linear(w, 4)`` with act ``Tanh`` or ``ReLU`` and w in 1..64.  ``ValueError`` on anything else."""
+        nn = torch.nn
+        if not isinstance(module, nn.Sequential):
+            raise ValueError("the policy must be an nn.Sequential of Linear / Tanh / ReLU layers")
+        layers = list(module)
+        if len(layers) not in (3, 5):
+            raise ValueError(f"the policy must have 1 or 2 hidden layers (3 or 5 modules), got {len(layers)} modules")
+        lin, act = layers[0::2], layers[1::2]
+        if not all(isinstance(m, nn.Linear) for m in lin) or not all(isinstance(m, (nn.Tanh, nn.ReLU)) for m in act):
+            raise ValueError("the policy must alternate Linear layers with Tanh or ReLU")
+        if len({type(m) for m in act}) != 1:
+            raise ValueError("the hidden layers must share one activation")
+        if any(m.bias is None for m in lin):
+            raise ValueError("every Linear layer needs its bias")
+        width = lin[0].out_features
+        if not 1 <= width <= capi.POLICY_MAX_WIDTH:
+            raise ValueError(f"the hidden width must be in 1..{capi.POLICY_MAX_WIDTH}, got {width}")
+        dims = [(m.in_features, m.out_features) for m in lin]
+        if dims != [(capi.POLICY_IN, width)] + [(width, width)] * (len(lin) - 2) + [(width, capi.POLICY_OUT)]:
+            raise ValueError(f"the layers must be {capi.POLICY_IN} -> width [-> width] -> {capi.POLICY_OUT} with one common width, got {dims}")
+        w = torch.cat([t.detach().double().flatten().cpu() for m in lin for t in (m.weight, m.bias)]).numpy()
+        return w, len(lin) - 1, width, "tanh" if isinstance(act[0], nn.Tanh) else "relu"
+
+    def set_episode_policy_from_torch(self, module, rpm_base=None, rpm_scale=None):
+        """``set_episode_policy`` from an ``nn.Sequential`` of ``Linear`` / ``Tanh`` / ``ReLU`` (stable-baselines3:
+        ``nn.Sequential(*model.policy.mlp_extractor.policy_net, model.policy.action_net)``).  ``ValueError`` on any other shape."""
+        w, n_hidden, width, activation = self._episode_policy_from_torch(module)
+        self.set_episode_policy(w, n_hidden, width, activation, rpm_base, rpm_scale)
+
+    def episode_policy_compute(self, obs: torch.Tensor):
+        """The policy alone on observation rows ``obs`` [E,D,20] (mds_episode_policy_compute): the commanded RPM [E,D,4], a new tensor.
+        Followed by ``step_episodes`` this is the policy-in-the-loop form of ``rollout_episodes_policy``."""
+        self._require_open()
+        if obs.dtype != self.dtype or not obs.is_contiguous() or obs.numel() != self.n * capi.OBS_DIM or obs.device != self._obs.device:
+            raise ValueError("obs must be a contiguous [E,D,20] device tensor of the env's dtype")
+        rpm = torch.empty((self.NUM_ENVS, self.NUM_DRONES, capi.ACT_DIM), dtype=self.dtype, device=self._obs.device)
+        capi.check(self._lib.mds_episode_policy_compute(self._h, C.c_void_p(obs.data_ptr()), C.c_void_p(rpm.data_ptr()), self._stream()),
+                   "mds_episode_policy_compute")
+        return rpm
+
+    def rollout_episodes_policy(self, first_step: int, n_steps: int, obs_log: torch.Tensor | None = None, action_log: torch.Tensor | None = None,
+                                reward_log: torch.Tensor | None = None, flags_log: torch.Tensor | None = None, steps_per_launch: int = 1):
+        """``n_steps`` control steps of the configured policy in closed loop with the episode rule, ``steps_per_launch`` per kernel
+        launch (mds_rollout_episodes_policy): every drone acts on its current state, post-reset where its env was just done.  Step j
+        writes slot ``j % T`` of each log given: ``obs_log`` [T,E,D,20], ``action_log`` [T,E,D,4] (the commanded RPM), ``reward_log``
+        [T,E], ``flags_log`` [T,E] int32, as in ``rollout_episodes``.  Returns the current observation [E,D,20]."""
+        self._require_open()
+        slots = set()
+        for name, log, dt, per in (("obs_log", obs_log, self.dtype, self.n * capi.OBS_DIM), ("action_log", action_log, self.dtype, self.n * capi.ACT_DIM),
+                                   ("reward_log", reward_log, self._episode_dtype(), self.NUM_ENVS), ("flags_log", flags_log, torch.int32, self.NUM_ENVS)):
+            if log is None:
+                continue
+            if log.dtype != dt or not log.is_contiguous() or log.numel() == 0 or log.numel() % per:
+                raise ValueError(f"{name} must be a contiguous tensor of dtype {dt} with {per} values per step")
+            slots.add(log.numel() // per)
+        if len(slots) > 1:
+            raise ValueError("obs_log, action_log, reward_log and flags_log must hold the same number of steps")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)   # noqa: E731
+        capi.check(self._lib.mds_rollout_episodes_policy(self._h, C.c_int(int(first_step)), C.c_int(int(n_steps)), ptr(obs_log),
+                                                         C.c_int(slots.pop() if slots else 0), ptr(action_log), ptr(reward_log), ptr(flags_log),
+                                                         C.c_int(int(steps_per_launch)), ptr(self._obs), self._stream()),
+                   "mds_rollout_episodes_policy")
+        self.step_counter += n_steps * self.PYB_STEPS_PER_CTRL
+        return self._obs
+
     def set_rollout_streams(self, n_streams: int = 0):
         """How rollout_geometric issues its steps: 0 auto, 1 the current stream only, 2 the two halves of the shard on two
         internal streams (mds_set_rollout_streams).  Same results either way."""
