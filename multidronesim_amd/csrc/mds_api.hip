@@ -493,6 +493,34 @@ template <typename T> static EpisodeRandomArgs<T> episode_random_args(const mds_
   a.rpy0 = h->init_pose + (size_t)3 * h->n;
   return a;
 }
+// what the two episode rollout entry points hand their kernels in compute type T, from the handle: the rule, the counters, the safety
+// and the randomisation blocks (zeroed where the handle has none), the workgroup's share of envs and the grid
+template <typename T> struct EpisodeLaunch {
+  EpisodeRule<T> rule;
+  EpisodeCounters<T> cnt;
+  EpisodeSafetyArgs<T> safe;
+  EpisodeRandomArgs<T> rnd;
+  int D, epb;
+  dim3 grid;
+};
+template <typename T> static EpisodeLaunch<T> episode_launch(const mds_handle* h) {
+  const mds_episode_params& p = h->ep;
+  EpisodeLaunch<T> a = {};
+  fill_episode_rule<T>(p.max_steps, p.z_min, p.z_max, p.max_dist, p.max_tilt, p.max_speed, p.max_rate, p.reward_r0, p.term_penalty, a.rule);
+  char* cb = (char*)h->ep_counters;
+  const size_t sl = h->ep_slots * 8;
+  a.cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
+  if (h->ep_safe) {
+    fill_episode_safety<T>(h->ep_safety.safety_radius, h->ep_safety.zscale, h->ep_safety.n_obs, h->ep_obstacles, a.safe.set);
+    a.safe.h_min_step = (T*)h->ep_hmin;
+    a.safe.h_min_episode = (T*)((char*)h->ep_hmin + sl);
+  }
+  if (h->ep_random) a.rnd = episode_random_args<T>(h);
+  a.D = h->cfg.num_drones;
+  a.epb = episode_envs_per_block(a.D);
+  a.grid = dim3((unsigned)((h->cfg.num_envs + a.epb - 1) / a.epb));
+  return a;
+}
 // the handle's policy as the kernels take it
 template <typename T> static EpisodePolicy<T> episode_policy_args(const mds_handle* h) {
   return {(const T*)h->ep_policy_w, h->ep_pol.n_hidden, h->ep_pol.activation, (T)h->ep_pol.rpm_base, (T)h->ep_pol.rpm_scale};
@@ -1464,41 +1492,26 @@ int mds_rollout_episodes(mds_handle* h, const void* actions, int n_action_sets, 
     return fail(MDS_EALIGN, "mds_rollout_episodes: obs_dev/reward_log_dev/flags_log_dev");
   if (!h->ep_on) return fail(MDS_ESTATE, "mds_rollout_episodes: no episodes configured (mds_set_episodes)");
   hipStream_t st = (hipStream_t)stream;
-  const int D = h->cfg.num_drones, epb = episode_envs_per_block(D);
-  const dim3 grid((unsigned)((h->cfg.num_envs + epb - 1) / epb));
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-  const mds_episode_params& p = h->ep;
   for (Chunks c{n_steps, steps_per_launch, 0.0, 0.0, ring ? first_step % log_slots : 0, ring ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
     const int ks = c.len(), a0 = (int)(((long long)first_step + c.k) % n_action_sets), s0 = c.slot;
     const bool last = c.k + ks == n_steps;
     with_flags([&](auto RK4, auto DRAG) {
       with_dtype(h->cfg.dtype, [&](auto DT) {
         using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
-        EpisodeRule<T> rule;
-        fill_episode_rule<T>(p.max_steps, p.z_min, p.z_max, p.max_dist, p.max_tilt, p.max_speed, p.max_rate, p.reward_r0, p.term_penalty, rule);
-        char* cb = (char*)h->ep_counters;
-        const size_t sl = h->ep_slots * 8;
-        const EpisodeCounters<T> cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
+        const EpisodeLaunch<T> ep = episode_launch<T>(h);
         // one launch, whichever of the four kernels: `extra` is what follows the counters (nothing | the safety set | the
         // randomisation | both, in this order)
         auto launch = [&](auto kernel, auto... extra) {
-          kernel<<<grid, kBlock, 0, st>>>(params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin,
-                                          (const T*)h->ep_target, (T*)rpm_track(h), (const S*)actions, a0, n_action_sets, (S*)obs_log,
-                                          (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks, (S*)(last ? obs : nullptr), cnt, extra...);
+          kernel<<<ep.grid, kBlock, 0, st>>>(params<T>(h).c, ep.rule, h->n, h->ld, ep.D, ep.epb, (S*)h->state, (const S*)h->ep_image,
+                                             (const T*)h->origin, (const T*)h->ep_target, (T*)rpm_track(h), (const S*)actions, a0, n_action_sets,
+                                             (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks, (S*)(last ? obs : nullptr),
+                                             ep.cnt, extra...);
         };
         using R = EpisodeRandomArgs<T>;
-        R rnd = {};
-        if (h->ep_random) rnd = episode_random_args<T>(h);
-        if (h->ep_safe) {
-          EpisodeSafetyArgs<T> safe;
-          fill_episode_safety<T>(h->ep_safety.safety_radius, h->ep_safety.zscale, h->ep_safety.n_obs, h->ep_obstacles, safe.set);
-          safe.h_min_step = (T*)h->ep_hmin;
-          safe.h_min_episode = (T*)((char*)h->ep_hmin + sl);
-          if (h->ep_random) launch(k_rollout_episodes_safe<T, S, RK4(), DRAG(), R>, safe, rnd);
-          else launch(k_rollout_episodes_safe<T, S, RK4(), DRAG()>, safe);
-          return;
-        }
-        if (h->ep_random) launch(k_rollout_episodes<T, S, RK4(), DRAG(), R>, rnd);
+        if (h->ep_safe && h->ep_random) launch(k_rollout_episodes_safe<T, S, RK4(), DRAG(), R>, ep.safe, ep.rnd);
+        else if (h->ep_safe) launch(k_rollout_episodes_safe<T, S, RK4(), DRAG()>, ep.safe);
+        else if (h->ep_random) launch(k_rollout_episodes<T, S, RK4(), DRAG(), R>, ep.rnd);
         else launch(k_rollout_episodes<T, S, RK4(), DRAG()>);
       });
     }, rk4, drag);
@@ -1588,37 +1601,22 @@ int mds_rollout_episodes_policy(mds_handle* h, int first_step, int n_steps, void
     return fail(MDS_EALIGN, "mds_rollout_episodes_policy: obs_dev/obs_log_dev/action_log_dev/reward_log_dev/flags_log_dev");
   if (!h->ep_on || !h->ep_policy) return fail(MDS_ESTATE, "mds_rollout_episodes_policy: no policy configured (mds_set_episodes, mds_set_episode_policy)");
   hipStream_t st = (hipStream_t)stream;
-  const int D = h->cfg.num_drones, epb = episode_envs_per_block(D);
-  const dim3 grid((unsigned)((h->cfg.num_envs + epb - 1) / epb));
   const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
-  const mds_episode_params& p = h->ep;
   for (Chunks c{n_steps, steps_per_launch, 0.0, 0.0, ring ? first_step % log_slots : 0, ring ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
     const int ks = c.len(), s0 = c.slot;
     const bool last = c.k + ks == n_steps;
     with_flags([&](auto RK4, auto DRAG) {
       with_policy_dtype(h->cfg.dtype, [&](auto DT) {
         using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
-        EpisodeRule<T> rule;
-        fill_episode_rule<T>(p.max_steps, p.z_min, p.z_max, p.max_dist, p.max_tilt, p.max_speed, p.max_rate, p.reward_r0, p.term_penalty, rule);
-        char* cb = (char*)h->ep_counters;
-        const size_t sl = h->ep_slots * 8;
-        const EpisodeCounters<T> cnt = {(int*)cb, (T*)(cb + sl), (int*)(cb + 2 * sl), (T*)(cb + 3 * sl), (int*)(cb + 4 * sl)};
-        EpisodeRandomArgs<T> rnd = {};
-        if (h->ep_random) rnd = episode_random_args<T>(h);
-        EpisodeSafetyArgs<T> safe = {};
-        if (h->ep_safe) {
-          fill_episode_safety<T>(h->ep_safety.safety_radius, h->ep_safety.zscale, h->ep_safety.n_obs, h->ep_obstacles, safe.set);
-          safe.h_min_step = (T*)h->ep_hmin;
-          safe.h_min_episode = (T*)((char*)h->ep_hmin + sl);
-        }
+        const EpisodeLaunch<T> ep = episode_launch<T>(h);
         with_int<32, 64>(h->ep_policy_width, [&](auto W) {
           // not built: float64, RK4, 32 wide -- the one combination whose register allocation leaves a (never accessed) slot in the private
           // segment; mds_set_episode_policy pads such a handle's policy to 64, which changes no bit
           if constexpr (!(RK4() && sizeof(T) == 8 && W() == 32))
-          k_rollout_episodes_policy<T, S, RK4(), DRAG(), W()><<<grid, kBlock, 0, st>>>(
-              params<T>(h).c, rule, h->n, h->ld, D, epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
+          k_rollout_episodes_policy<T, S, RK4(), DRAG(), W()><<<ep.grid, kBlock, 0, st>>>(
+              params<T>(h).c, ep.rule, h->n, h->ld, ep.D, ep.epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
               (T*)rpm_track(h), episode_policy_args<T>(h), (S*)action_log, (S*)obs_log, (T*)reward_log, (int*)flags_log, s0, ring ? log_slots : 1, ks,
-              (S*)(last ? obs : nullptr), cnt, h->ep_safe ? 1 : 0, safe, h->ep_random ? 1 : 0, rnd);
+              (S*)(last ? obs : nullptr), ep.cnt, h->ep_safe ? 1 : 0, ep.safe, h->ep_random ? 1 : 0, ep.rnd);
         });
       });
     }, rk4, drag);

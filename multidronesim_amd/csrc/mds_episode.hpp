@@ -136,4 +136,38 @@ template <typename T> MDS_HD T episode_reward(const EpisodeRule<T>& r, T sum_ter
   return (flags & kEpTerminated) ? sum_terms - r.term_penalty : sum_terms;
 }
 
+// an env's counters as its step carries them: the running episode's length and return, and of the completed episodes their number,
+// summed returns, summed lengths.  (A plain aggregate on purpose: with default member initialisers the rollout kernels that hold one
+// come out in another instruction order.)
+template <typename T> struct EpisodeTally {
+  int length, count, sum_length;
+  T ret, sum_return;
+};
+// what a step of the env hands back
+template <typename T> struct EpisodeStep {
+  int flags;
+  T reward;
+  bool done;
+};
+// One control step of an env, from the OR of its drones' cause bits and the sum of their reward terms: the episode grows by the step,
+// flags and reward follow from the rule, and a done episode (terminated or truncated) goes into the completed ones and leaves a fresh
+// tally.  The statement of the env's step for the host (tests/test_episode_cpu.py carries it over steps and envs against the oracle's
+// counter lines).  The three rollout kernels write these lines out in their loops, with the log stores between `ret += reward` and the
+// done part (mds_episode_kernels.hip says why); they are to be kept equal to this function.
+template <typename T> MDS_HD EpisodeStep<T> episode_env_step(const EpisodeRule<T>& r, int causes, T sum_terms, EpisodeTally<T>& t) {
+  ++t.length;
+  const int flags = episode_flags(r, causes, t.length);
+  const T reward = episode_reward(r, sum_terms, flags);
+  t.ret += reward;
+  const bool done = (flags & (kEpTerminated | kEpTruncated)) != 0;
+  if (done) {
+    ++t.count;
+    t.sum_return += t.ret;
+    t.sum_length += t.length;
+    t.length = 0;
+    t.ret = T(0);
+  }
+  return {flags, reward, done};
+}
+
 }  // namespace mds

@@ -17,11 +17,14 @@
 // k_rollout_episodes_safe is k_rollout_episodes with the collision causes of mds_set_episode_safety (bits 6 and 7, the env's smallest
 // h).  The drones of an env already share a workgroup, so the pairwise test is one more exchange through LDS: positions out, barrier,
 // the D - 1 env-mates read back.  That makes two barriers per step and lets every exchanged array stay single-buffered (the argument
-// stands in the kernel).  It is a sibling kernel, not a flag of the first: a body shared through an inlined function reads the
-// by-value argument blocks differently, and the instructions of the existing kernel were to stay as they are
-// (profiles/asm_equiv_episode_safety.md).  Its loop is the first kernel's line for line, with the SAFE blocks added; a change to one
-// is a change to both.  LDS of the sibling: observation staging + 5 words (cause, term, h) + 3 position and 3 origin words per lane
+// stands in the kernel).  LDS of the sibling: observation staging + 5 words (cause, term, h) + 3 position and 3 origin words per lane
 // = 58 368 B in float64, 29 696 B in float32, 19 456 B with fp16 storage.
+//
+// Shared and written out.  The two kernels here and k_rollout_episodes_policy (mds_episode_policy_kernels.hip) share the lane map
+// (EpisodeLane) and the type of the env's counters (mds_episode.hpp EpisodeTally); the env's step is stated for the host in
+// mds_episode.hpp episode_env_step, and each kernel's loop writes the same lines out.  Why: these kernels keep the instruction order
+// they had, the only one measured to be as fast, and any function over the tally or the counters changes it, as does one body under
+// a SAFE flag (profiles/asm_equiv_episode_pieces.md, asm_equiv_episode_safety.md).  A change to one loop is a change to all three.
 #include "mds_episode.hpp"
 #include "mds_episode_random.hpp"
 
@@ -88,6 +91,26 @@ __global__ __launch_bounds__(kBlock) void k_episode_reset_random(const int n, co
   if (obs != nullptr) write_obs_rows<S, T>(lds, obs, n, i, valid, o);
 }
 
+// Where a thread stands: drone i of the handle, drone d of env e of E (the block's envs start at lane 0, D lanes each); block_end
+// bounds the block's rows for write_obs_rows.  (b = tid - d stays in the kernels; the statements keep this order: both for the assembly.)
+struct EpisodeLane {
+  int tid, i, block_end, d, e, E;
+  bool valid;
+};
+__device__ __forceinline__ EpisodeLane episode_lane(int envs_per_block, int D, int n) {
+  EpisodeLane L;
+  L.tid = (int)threadIdx.x;
+  const int per_block = envs_per_block * D, first = (int)blockIdx.x * per_block;
+  L.i = first + L.tid;
+  L.block_end = min(first + per_block, n);                  // n = E * D: whole envs
+  L.valid = L.tid < per_block && L.i < n;
+  const int le = L.tid / D;                                 // env within the block
+  L.d = L.tid - le * D;
+  L.E = n / D;
+  L.e = (int)blockIdx.x * envs_per_block + le;
+  return L;
+}
+
 // The trailing pack RND is empty -- the kernel of a handle without randomisation, argument for argument what it was before the pack
 // existed -- or one EpisodeRandomArgs<T>: the reset arm then moves the image's state by the draw.  The arm runs only in waves where a
 // lane is done (the branch is skipped on an empty mask), at a point where the stepped state is dead: the 3 x 40 integer multiplies of
@@ -103,73 +126,65 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes(const Consts<T> c, 
   __shared__ __align__(16) unsigned char lds[kBlock * kObsDim * sizeof(S)];
   __shared__ int red_cause[2][kBlock];
   __shared__ T red_term[2][kBlock];
-  const int tid = (int)threadIdx.x;
-  const int per_block = envs_per_block * D;
-  const int first = (int)blockIdx.x * per_block;
-  const int i = first + tid;
-  const int block_end = min(first + per_block, n);          // n = E * D: whole envs
-  const bool valid = tid < per_block && i < n;
-  const int le = tid / D, d = tid - le * D;                 // env within the block, drone within the env
-  const int E = n / D, e = (int)blockIdx.x * envs_per_block + le;
+  const EpisodeLane L = episode_lane(envs_per_block, D, n);
   State<T> s;
   Resid<T> r;
   resid_zero(r);
   V3<T> org = {T(0), T(0), T(0)}, home = org, tgt = org;
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
-  int length = 0, count = 0, sum_length = 0;
-  T ret = T(0), sum_return = T(0);
-  if (valid) {
-    load_state<S, T>(state, ld, i, s);
-    org = load_origin(origin, ld, i);
-    home = {(T)image[sidx(0, i, ld)], (T)image[sidx(1, i, ld)], (T)image[sidx(2, i, ld)]};
-    tgt = load_origin(target, ld, i);       // (held across the loop: reloading both per step frees no register and measured no faster)
+  EpisodeTally<T> t = {0, 0, 0, T(0), T(0)};
+  if (L.valid) {
+    load_state<S, T>(state, ld, L.i, s);
+    org = load_origin(origin, ld, L.i);
+    home = {(T)image[sidx(0, L.i, ld)], (T)image[sidx(1, L.i, ld)], (T)image[sidx(2, L.i, ld)]};
+    tgt = load_origin(target, ld, L.i);       // (held across the loop: reloading both per step frees no register and measured no faster)
     if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    length = cnt.length[e]; ret = cnt.ret[e];
-    count = cnt.count[e]; sum_return = cnt.sum_return[e]; sum_length = cnt.sum_length[e];
+      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + L.i];
+    t.length = cnt.length[L.e]; t.ret = cnt.ret[L.e];
+    t.count = cnt.count[L.e]; t.sum_return = cnt.sum_return[L.e]; t.sum_length = cnt.sum_length[L.e];
   }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     int cause = 0;
     T term = T(0);
-    if (valid) {
+    if (L.valid) {
       T act[4];
-      load4<S, T>(actions + ((size_t)a0 * n + i) * 4, act);
+      load4<S, T>(actions + ((size_t)a0 * n + L.i) * 4, act);
       aviary_step_any<T, RK4, DRAG, false>(c, s, r, act, prev, clipped);
       if (obs_log != nullptr) pack_obs(s, org, clipped, o);
       cause = episode_causes(rule, s, s.p.z + org.z, home);
       term = episode_reward_term(rule, s.p, tgt);
     }
     // the logged row is the transition's result: before any reset
-    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, block_end, i, valid, o);
+    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, L.block_end, L.i, L.valid, o);
     const int par = k & 1;
-    red_cause[par][tid] = cause;
-    red_term[par][tid] = term;
+    red_cause[par][L.tid] = cause;
+    red_term[par][L.tid] = term;
     __syncthreads();
-    if (valid) {
-      const int b = tid - d;
+    if (L.valid) {
+      const int b = L.tid - L.d;
       int causes = 0;
       T sum = T(0);
       for (int j = 0; j < D; ++j) {                          // drone order d = 0 .. D-1
         causes |= red_cause[par][b + j];
         sum += red_term[par][b + j];
       }
-      ++length;
-      const int flags = episode_flags(rule, causes, length);
+      ++t.length;
+      const int flags = episode_flags(rule, causes, t.length);
       const T reward = episode_reward(rule, sum, flags);
-      ret += reward;
-      if (d == 0) {
-        if (reward_log != nullptr) reward_log[(size_t)s0 * E + e] = reward;
-        if (flags_log != nullptr) flags_log[(size_t)s0 * E + e] = flags;
+      t.ret += reward;
+      if (L.d == 0) {
+        if (reward_log != nullptr) reward_log[(size_t)s0 * L.E + L.e] = reward;
+        if (flags_log != nullptr) flags_log[(size_t)s0 * L.E + L.e] = flags;
       }
       if (flags & (kEpTerminated | kEpTruncated)) {
-        ++count;
-        sum_return += ret;
-        sum_length += length;
-        length = 0;
-        ret = T(0);
-        load_state<S, T>(image, ld, i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
-        if constexpr (sizeof...(RND) != 0) episode_random_reset<S, T>(rnd..., i, count, s);      // ... moved by the episode's draw
+        ++t.count;
+        t.sum_return += t.ret;
+        t.sum_length += t.length;
+        t.length = 0;
+        t.ret = T(0);
+        load_state<S, T>(image, ld, L.i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
+        if constexpr (sizeof...(RND) != 0) episode_random_reset<S, T>(rnd..., L.i, t.count, s);      // ... moved by the episode's draw
         for (int j = 0; j < 4; ++j) prev[j] = clipped[j] = T(0);
       }
     }
@@ -178,15 +193,15 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes(const Consts<T> c, 
   }
   if (obs_now != nullptr) {                                  // the current observation: after the resets
     T o[kObsDim];
-    if (valid) pack_obs(s, org, clipped, o);
-    write_obs_rows<S, T>(lds, obs_now, block_end, i, valid, o);
+    if (L.valid) pack_obs(s, org, clipped, o);
+    write_obs_rows<S, T>(lds, obs_now, L.block_end, L.i, L.valid, o);
   }
-  if (valid) {
-    store_state<S, T>(state, ld, i, s);
-    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
-    if (d == 0) {
-      cnt.length[e] = length; cnt.ret[e] = ret;
-      cnt.count[e] = count; cnt.sum_return[e] = sum_return; cnt.sum_length[e] = sum_length;
+  if (L.valid) {
+    store_state<S, T>(state, ld, L.i, s);
+    store_last_rpm<DRAG>(last_rpm, ld, L.i, clipped);
+    if (L.d == 0) {
+      cnt.length[L.e] = t.length; cnt.ret[L.e] = t.ret;
+      cnt.count[L.e] = t.count; cnt.sum_return[L.e] = t.sum_return; cnt.sum_length[L.e] = t.sum_length;
     }
   }
 }
@@ -240,50 +255,42 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T
   __shared__ int red_cause[kBlock];
   __shared__ T red_term[kBlock], red_h[kBlock];
   __shared__ T pos_x[kBlock], pos_y[kBlock], pos_z[kBlock], org_x[kBlock], org_y[kBlock], org_z[kBlock];
-  const int tid = (int)threadIdx.x;
-  const int per_block = envs_per_block * D;
-  const int first = (int)blockIdx.x * per_block;
-  const int i = first + tid;
-  const int block_end = min(first + per_block, n);          // n = E * D: whole envs
-  const bool valid = tid < per_block && i < n;
-  const int le = tid / D, d = tid - le * D;                 // env within the block, drone within the env
-  const int E = n / D, e = (int)blockIdx.x * envs_per_block + le;
-  const int b = tid - d;                                    // the env's first lane: lanes b .. b + D - 1 are its drones, valid when this one is
+  const EpisodeLane L = episode_lane(envs_per_block, D, n);
+  const int b = L.tid - L.d;                                // the env's first lane: lanes b .. b + D - 1 are its drones, valid when this one is
   State<T> s;
   Resid<T> r;
   resid_zero(r);
   V3<T> org = {T(0), T(0), T(0)}, home = org, tgt = org;
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
-  int length = 0, count = 0, sum_length = 0;
-  T ret = T(0), sum_return = T(0);
+  EpisodeTally<T> t = {0, 0, 0, T(0), T(0)};
   T h_step = T(INFINITY), h_episode = T(INFINITY);          // the env's smallest h of the last step, and of its running episode
-  if (valid) {
-    load_state<S, T>(state, ld, i, s);
-    org = load_origin(origin, ld, i);
-    home = {(T)image[sidx(0, i, ld)], (T)image[sidx(1, i, ld)], (T)image[sidx(2, i, ld)]};
-    tgt = load_origin(target, ld, i);
+  if (L.valid) {
+    load_state<S, T>(state, ld, L.i, s);
+    org = load_origin(origin, ld, L.i);
+    home = {(T)image[sidx(0, L.i, ld)], (T)image[sidx(1, L.i, ld)], (T)image[sidx(2, L.i, ld)]};
+    tgt = load_origin(target, ld, L.i);
     if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    length = cnt.length[e]; ret = cnt.ret[e];
-    count = cnt.count[e]; sum_return = cnt.sum_return[e]; sum_length = cnt.sum_length[e];
-    h_episode = safe.h_min_episode[e];
-    org_x[tid] = org.x; org_y[tid] = org.y; org_z[tid] = org.z;   // constant over the launch: staged once, published by barrier A of step 0
+      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + L.i];
+    t.length = cnt.length[L.e]; t.ret = cnt.ret[L.e];
+    t.count = cnt.count[L.e]; t.sum_return = cnt.sum_return[L.e]; t.sum_length = cnt.sum_length[L.e];
+    h_episode = safe.h_min_episode[L.e];
+    org_x[L.tid] = org.x; org_y[L.tid] = org.y; org_z[L.tid] = org.z;   // constant over the launch: staged once, published by barrier A of step 0
   }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     int cause = 0;
     T term = T(0), h_lane = T(INFINITY);
-    if (valid) {
+    if (L.valid) {
       T act[4];
-      load4<S, T>(actions + ((size_t)a0 * n + i) * 4, act);
+      load4<S, T>(actions + ((size_t)a0 * n + L.i) * 4, act);
       aviary_step_any<T, RK4, DRAG, false>(c, s, r, act, prev, clipped);
       if (obs_log != nullptr) pack_obs(s, org, clipped, o);
       cause = episode_causes(rule, s, s.p.z + org.z, home);
       term = episode_reward_term(rule, s.p, tgt);
-      pos_x[tid] = s.p.x; pos_y[tid] = s.p.y; pos_z[tid] = s.p.z;           // the stepped, pre-reset local position
+      pos_x[L.tid] = s.p.x; pos_y[L.tid] = s.p.y; pos_z[L.tid] = s.p.z;           // the stepped, pre-reset local position
     }
     // the logged row is the transition's result: before any reset
-    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, block_end, i, valid, o);
+    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, L.block_end, L.i, L.valid, o);
     // Two barriers per step.  A: every lane has published its position.  B: every lane has published its cause word, reward term and
     // smallest h.  pos_* is written before A and read between A and B; red_* is written between A and B and read after B.  A wave
     // writes pos_* of step k + 1 only after it has passed B of step k, which every wave reaches after its pos_* reads of step k; it
@@ -291,12 +298,12 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T
     // overwritten while a wave one barrier behind still reads it, and no array needs a parity copy.  org_* is written once, before
     // the first A, and only read afterwards.  (write_obs_rows stages within a wave: it takes no part in this.)
     __syncthreads();                                                         // A
-    if (valid) h_lane = episode_safety_lane(safe.set, pos_x, pos_y, pos_z, org_x, org_y, org_z, b, d, D, s.p, org, cause);
-    red_cause[tid] = cause;
-    red_term[tid] = term;
-    red_h[tid] = h_lane;
+    if (L.valid) h_lane = episode_safety_lane(safe.set, pos_x, pos_y, pos_z, org_x, org_y, org_z, b, L.d, D, s.p, org, cause);
+    red_cause[L.tid] = cause;
+    red_term[L.tid] = term;
+    red_h[L.tid] = h_lane;
     __syncthreads();                                                         // B
-    if (valid) {
+    if (L.valid) {
       int causes = 0;
       T sum = T(0);
       h_step = T(INFINITY);
@@ -306,23 +313,23 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T
         h_step = m_min(red_h[b + j], h_step);
       }
       h_episode = m_min(h_step, h_episode);
-      ++length;
-      const int flags = episode_flags(rule, causes, length);
+      ++t.length;
+      const int flags = episode_flags(rule, causes, t.length);
       const T reward = episode_reward(rule, sum, flags);
-      ret += reward;
-      if (d == 0) {
-        if (reward_log != nullptr) reward_log[(size_t)s0 * E + e] = reward;
-        if (flags_log != nullptr) flags_log[(size_t)s0 * E + e] = flags;
+      t.ret += reward;
+      if (L.d == 0) {
+        if (reward_log != nullptr) reward_log[(size_t)s0 * L.E + L.e] = reward;
+        if (flags_log != nullptr) flags_log[(size_t)s0 * L.E + L.e] = flags;
       }
       if (flags & (kEpTerminated | kEpTruncated)) {
-        ++count;
-        sum_return += ret;
-        sum_length += length;
-        length = 0;
-        ret = T(0);
+        ++t.count;
+        t.sum_return += t.ret;
+        t.sum_length += t.length;
+        t.length = 0;
+        t.ret = T(0);
         h_episode = T(INFINITY);
-        load_state<S, T>(image, ld, i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
-        if constexpr (sizeof...(RND) != 0) episode_random_reset<S, T>(rnd..., i, count, s);      // ... moved by the episode's draw
+        load_state<S, T>(image, ld, L.i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
+        if constexpr (sizeof...(RND) != 0) episode_random_reset<S, T>(rnd..., L.i, t.count, s);      // ... moved by the episode's draw
         for (int j = 0; j < 4; ++j) prev[j] = clipped[j] = T(0);
       }
     }
@@ -331,17 +338,17 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_safe(const Consts<T
   }
   if (obs_now != nullptr) {                                  // the current observation: after the resets
     T o[kObsDim];
-    if (valid) pack_obs(s, org, clipped, o);
-    write_obs_rows<S, T>(lds, obs_now, block_end, i, valid, o);
+    if (L.valid) pack_obs(s, org, clipped, o);
+    write_obs_rows<S, T>(lds, obs_now, L.block_end, L.i, L.valid, o);
   }
-  if (valid) {
-    store_state<S, T>(state, ld, i, s);
-    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
-    if (d == 0) {
-      cnt.length[e] = length; cnt.ret[e] = ret;
-      cnt.count[e] = count; cnt.sum_return[e] = sum_return; cnt.sum_length[e] = sum_length;
-      if (n_steps > 0) safe.h_min_step[e] = h_step;
-      safe.h_min_episode[e] = h_episode;
+  if (L.valid) {
+    store_state<S, T>(state, ld, L.i, s);
+    store_last_rpm<DRAG>(last_rpm, ld, L.i, clipped);
+    if (L.d == 0) {
+      cnt.length[L.e] = t.length; cnt.ret[L.e] = t.ret;
+      cnt.count[L.e] = t.count; cnt.sum_return[L.e] = t.sum_return; cnt.sum_length[L.e] = t.sum_length;
+      if (n_steps > 0) safe.h_min_step[L.e] = h_step;
+      safe.h_min_episode[L.e] = h_episode;
     }
   }
 }

@@ -1,12 +1,12 @@
 // An MLP policy inside the episode rollout kernel (include/mds.h mds_rollout_episodes_policy; the arithmetic: mds_policy.hpp).
 //
-// k_rollout_episodes_policy is k_rollout_episodes_safe's loop (mds_episode_kernels.hip: the same per-drone pieces, the same
-// whole-envs-per-workgroup mapping, the same two barriers per step and single-buffered exchange arrays) with the read of the action
-// table replaced by the policy: at the top of every step a lane forms the 12 features of its drone from the state it holds -- the
-// post-reset state where its env was just done, the loaded state at the first step of a launch -- evaluates the network and commands
-// the resulting RPM, which goes through aviary_step_any like a table action and, where a ring is given, into the action log.
-// The collision causes and the randomised starts are run-time flags here, not sibling kernels (wave-uniform branches; this kernel has
-// no older instruction stream to preserve): with the collision causes off barrier A still runs and the position exchange does not.
+// k_rollout_episodes_policy is k_rollout_episodes_safe (mds_episode_kernels.hip: the same lane map and tally, the same two barriers per
+// step and single-buffered exchange arrays, the loop written out here as there and for the reason given there) with the read of the
+// action table replaced by the policy: at the top of every step a lane forms the 12 features of its drone from the state it holds --
+// the post-reset state where its env was just done, the loaded state at the first step of a launch -- evaluates the network and
+// commands the resulting RPM, which goes through aviary_step_any like a table action and, where a ring is given, into the action log.
+// The collision causes and the randomised starts are run-time flags here, not sibling kernels (wave-uniform branches): with the
+// collision causes off barrier A still runs and the position exchange does not.
 //
 // Weights.  They are the same for every lane, so they are wave-uniform operands.  Route taken: scalar loads.  The handle keeps the
 // padded weights in device memory that nothing writes while a launch reads it; the kernels read them through a constant-address-space
@@ -107,42 +107,34 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_policy(const Consts
   __shared__ int red_cause[kBlock];
   __shared__ T red_term[kBlock], red_h[kBlock];
   __shared__ T pos_x[kBlock], pos_y[kBlock], pos_z[kBlock], org_x[kBlock], org_y[kBlock], org_z[kBlock];
-  const int tid = (int)threadIdx.x;
-  const int per_block = envs_per_block * D;
-  const int first = (int)blockIdx.x * per_block;
-  const int i = first + tid;
-  const int block_end = min(first + per_block, n);          // n = E * D: whole envs
-  const bool valid = tid < per_block && i < n;
-  const int le = tid / D, d = tid - le * D;                 // env within the block, drone within the env
-  const int E = n / D, e = (int)blockIdx.x * envs_per_block + le;
-  const int b = tid - d;                                    // the env's first lane: lanes b .. b + D - 1 are its drones, valid when this one is
+  const EpisodeLane L = episode_lane(envs_per_block, D, n);
+  const int b = L.tid - L.d;                                // the env's first lane: lanes b .. b + D - 1 are its drones, valid when this one is
   State<T> s;
   Resid<T> r;
   resid_zero(r);
   V3<T> org = {T(0), T(0), T(0)}, home = org, tgt = org;
   T prev[4] = {T(0), T(0), T(0), T(0)}, clipped[4] = {T(0), T(0), T(0), T(0)};
-  int length = 0, count = 0, sum_length = 0;
-  T ret = T(0), sum_return = T(0);
+  EpisodeTally<T> t = {0, 0, 0, T(0), T(0)};
   T h_step = T(INFINITY), h_episode = T(INFINITY);          // the env's smallest h of the last step, and of its running episode
-  if (valid) {
-    load_state<S, T>(state, ld, i, s);
-    org = load_origin(origin, ld, i);
-    home = {(T)image[sidx(0, i, ld)], (T)image[sidx(1, i, ld)], (T)image[sidx(2, i, ld)]};
-    tgt = load_origin(target, ld, i);
+  if (L.valid) {
+    load_state<S, T>(state, ld, L.i, s);
+    org = load_origin(origin, ld, L.i);
+    home = {(T)image[sidx(0, L.i, ld)], (T)image[sidx(1, L.i, ld)], (T)image[sidx(2, L.i, ld)]};
+    tgt = load_origin(target, ld, L.i);
     if (DRAG)
-      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + i];
-    length = cnt.length[e]; ret = cnt.ret[e];
-    count = cnt.count[e]; sum_return = cnt.sum_return[e]; sum_length = cnt.sum_length[e];
+      for (int k = 0; k < 4; ++k) prev[k] = last_rpm[k * ld + L.i];
+    t.length = cnt.length[L.e]; t.ret = cnt.ret[L.e];
+    t.count = cnt.count[L.e]; t.sum_return = cnt.sum_return[L.e]; t.sum_length = cnt.sum_length[L.e];
     if (safe_on) {
-      h_episode = safe.h_min_episode[e];
-      org_x[tid] = org.x; org_y[tid] = org.y; org_z[tid] = org.z;   // constant over the launch: staged once, published by barrier A of step 0
+      h_episode = safe.h_min_episode[L.e];
+      org_x[L.tid] = org.x; org_y[L.tid] = org.y; org_z[L.tid] = org.z;   // constant over the launch: staged once, published by barrier A of step 0
     }
   }
   for (int k = 0; k < n_steps; ++k) {
     T o[kObsDim];
     int cause = 0;
     T term = T(0), h_lane = T(INFINITY);
-    if (valid) {
+    if (L.valid) {
       // the policy acts on the state the lane holds: the features are the columns pack_obs would form of it
       T x[kPolicyIn], act[4];
       {
@@ -150,26 +142,26 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_policy(const Consts
         policy_features(s.p, tgt, rpy_from_rot(F.R, s.q), s.v, F.av, x);
       }
       episode_policy_act<T, W>(pol, x, act);
-      if (action_log != nullptr) store4<S, T>(action_log + ((size_t)s0 * n + i) * 4, act);
+      if (action_log != nullptr) store4<S, T>(action_log + ((size_t)s0 * n + L.i) * 4, act);
       aviary_step_any<T, RK4, DRAG, false>(c, s, r, act, prev, clipped);
       if (obs_log != nullptr) pack_obs(s, org, clipped, o);
       cause = episode_causes(rule, s, s.p.z + org.z, home);
       term = episode_reward_term(rule, s.p, tgt);
       if (safe_on) {
-        pos_x[tid] = s.p.x; pos_y[tid] = s.p.y; pos_z[tid] = s.p.z;         // the stepped, pre-reset local position
+        pos_x[L.tid] = s.p.x; pos_y[L.tid] = s.p.y; pos_z[L.tid] = s.p.z;         // the stepped, pre-reset local position
       }
     }
     // the logged row is the transition's result: before any reset
-    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, block_end, i, valid, o);
+    if (obs_log != nullptr) write_obs_rows<S, T>(lds, obs_log + (size_t)s0 * n * kObsDim, L.block_end, L.i, L.valid, o);
     // Two barriers per step, single-buffered arrays: the argument stands in k_rollout_episodes_safe and does not depend on what is
     // computed between the barriers (with the collision causes off nothing is exchanged between A and B, and red_* keep their order).
     __syncthreads();                                                         // A
-    if (safe_on && valid) h_lane = episode_safety_lane(safe.set, pos_x, pos_y, pos_z, org_x, org_y, org_z, b, d, D, s.p, org, cause);
-    red_cause[tid] = cause;
-    red_term[tid] = term;
-    red_h[tid] = h_lane;
+    if (safe_on && L.valid) h_lane = episode_safety_lane(safe.set, pos_x, pos_y, pos_z, org_x, org_y, org_z, b, L.d, D, s.p, org, cause);
+    red_cause[L.tid] = cause;
+    red_term[L.tid] = term;
+    red_h[L.tid] = h_lane;
     __syncthreads();                                                         // B
-    if (valid) {
+    if (L.valid) {
       int causes = 0;
       T sum = T(0);
       h_step = T(INFINITY);
@@ -179,23 +171,23 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_policy(const Consts
         h_step = m_min(red_h[b + j], h_step);
       }
       h_episode = m_min(h_step, h_episode);
-      ++length;
-      const int flags = episode_flags(rule, causes, length);
+      ++t.length;
+      const int flags = episode_flags(rule, causes, t.length);
       const T reward = episode_reward(rule, sum, flags);
-      ret += reward;
-      if (d == 0) {
-        if (reward_log != nullptr) reward_log[(size_t)s0 * E + e] = reward;
-        if (flags_log != nullptr) flags_log[(size_t)s0 * E + e] = flags;
+      t.ret += reward;
+      if (L.d == 0) {
+        if (reward_log != nullptr) reward_log[(size_t)s0 * L.E + L.e] = reward;
+        if (flags_log != nullptr) flags_log[(size_t)s0 * L.E + L.e] = flags;
       }
       if (flags & (kEpTerminated | kEpTruncated)) {
-        ++count;
-        sum_return += ret;
-        sum_length += length;
-        length = 0;
-        ret = T(0);
+        ++t.count;
+        t.sum_return += t.ret;
+        t.sum_length += t.length;
+        t.length = 0;
+        t.ret = T(0);
         h_episode = T(INFINITY);
-        load_state<S, T>(image, ld, i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
-        if (random_on) episode_random_reset<S, T>(rnd, i, count, s);      // ... moved by the episode's draw
+        load_state<S, T>(image, ld, L.i, s);                   // the library's reset, bit for bit (k_reset wrote the image)
+        if (random_on) episode_random_reset<S, T>(rnd, L.i, t.count, s);      // ... moved by the episode's draw
         for (int j = 0; j < 4; ++j) prev[j] = clipped[j] = T(0);
       }
     }
@@ -203,18 +195,18 @@ __global__ __launch_bounds__(kBlock) void k_rollout_episodes_policy(const Consts
   }
   if (obs_now != nullptr) {                                  // the current observation: after the resets
     T o[kObsDim];
-    if (valid) pack_obs(s, org, clipped, o);
-    write_obs_rows<S, T>(lds, obs_now, block_end, i, valid, o);
+    if (L.valid) pack_obs(s, org, clipped, o);
+    write_obs_rows<S, T>(lds, obs_now, L.block_end, L.i, L.valid, o);
   }
-  if (valid) {
-    store_state<S, T>(state, ld, i, s);
-    store_last_rpm<DRAG>(last_rpm, ld, i, clipped);
-    if (d == 0) {
-      cnt.length[e] = length; cnt.ret[e] = ret;
-      cnt.count[e] = count; cnt.sum_return[e] = sum_return; cnt.sum_length[e] = sum_length;
+  if (L.valid) {
+    store_state<S, T>(state, ld, L.i, s);
+    store_last_rpm<DRAG>(last_rpm, ld, L.i, clipped);
+    if (L.d == 0) {
+      cnt.length[L.e] = t.length; cnt.ret[L.e] = t.ret;
+      cnt.count[L.e] = t.count; cnt.sum_return[L.e] = t.sum_return; cnt.sum_length[L.e] = t.sum_length;
       if (safe_on) {
-        if (n_steps > 0) safe.h_min_step[e] = h_step;
-        safe.h_min_episode[e] = h_episode;
+        if (n_steps > 0) safe.h_min_step[L.e] = h_step;
+        safe.h_min_episode[L.e] = h_episode;
       }
     }
   }

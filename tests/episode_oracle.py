@@ -73,6 +73,28 @@ def env_flags(params, cause_env, length):
     return term * TERMINATED + trunc * TRUNCATED + (cause_env << CAUSE_SHIFT)
 
 
+def tally_step(params, t, cause_env, term_sum):
+    """One control step of E envs' counters (mds_episode.hpp episode_env_step).  t holds the arrays length, count, sum_length (integer) and
+    ret, sum_return (float64 or float32: the step's arithmetic runs in their dtype), each [E], and is updated in place; cause_env [E] is the
+    OR of each env's cause bits, term_sum [E] the sum of its reward terms.  -> flags, reward, done, and the length the episode had reached."""
+    p = {**PARAM_DEFAULTS, **params}
+    ft = t.ret.dtype.type
+    t.length += 1
+    flags = env_flags(p, cause_env, t.length)
+    length = t.length.copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        term_sum = np.asarray(term_sum, dtype=ft)
+        reward = np.where(flags & TERMINATED, term_sum - ft(p["term_penalty"]), term_sum)
+        t.ret += reward
+        done = (flags & (TERMINATED | TRUNCATED)) != 0
+        t.count += done
+        t.sum_return[done] += t.ret[done]
+    t.sum_length[done] += t.length[done]
+    t.length[done] = 0
+    t.ret[done] = 0.0
+    return flags, reward, done, length
+
+
 class EpisodeOracle:
     """AviaryOracle + the episode rule, for E envs of D drones (drone i belongs to env i // D)."""
 
@@ -106,24 +128,14 @@ class EpisodeOracle:
         state = np.concatenate([av.pos, av.quat, av.vel, av.rates], axis=-1)
         cause, margin = causes_and_margin(p, av.pos, av.quat, av.vel, (av.rates ** 2).sum(-1), np.isfinite(state).all(-1), self.home)
         cause_env = np.bitwise_or.reduce(cause.reshape(E, D), axis=1)
-        self.length += 1
-        flags = env_flags(p, cause_env, self.length)
-        length = self.length.copy()
         with np.errstate(invalid="ignore", over="ignore"):
             d2 = ((av.pos - self.target) ** 2).sum(-1)
             v = p["reward_r0"] - d2 * d2
         terms = np.where(v > 0, v, 0.0).reshape(E, D)
-        reward = np.zeros(E)
+        term_sum = np.zeros(E)
         for d in range(D):                                   # drone order
-            reward = reward + terms[:, d]
-        reward = np.where(flags & TERMINATED, reward - p["term_penalty"], reward)
-        self.ret += reward
-        done = (flags & (TERMINATED | TRUNCATED)) != 0
-        self.count += done
-        self.sum_return += np.where(done, self.ret, 0.0)
-        self.sum_length += np.where(done, self.length, 0)
-        self.length[done] = 0
-        self.ret[done] = 0.0
+            term_sum = term_sum + terms[:, d]
+        flags, reward, done, length = tally_step(p, self, cause_env, term_sum)
         if done.any():
             self._reset_envs(done)
         return dict(obs=obs, reward=reward, flags=flags.astype(np.int64), margin=margin.reshape(E, D).min(axis=1), cause=cause,

@@ -66,24 +66,14 @@ class EpisodeSafetyOracle(EO.EpisodeOracle):
         cause_env = np.bitwise_or.reduce(cause.reshape(E, D), axis=1)
         h_min_step = h_drone.reshape(E, D).min(axis=1)
         self.h_min_episode = np.minimum(self.h_min_episode, h_min_step)
-        self.length += 1
-        flags = EO.env_flags(p, cause_env, self.length)
-        length = self.length.copy()
         with np.errstate(invalid="ignore", over="ignore"):
             d2 = ((av.pos - self.target) ** 2).sum(-1)
             v = p["reward_r0"] - d2 * d2
         terms = np.where(v > 0, v, 0.0).reshape(E, D)
-        reward = np.zeros(E)
+        term_sum = np.zeros(E)
         for d in range(D):                                   # drone order
-            reward = reward + terms[:, d]
-        reward = np.where(flags & EO.TERMINATED, reward - p["term_penalty"], reward)
-        self.ret += reward
-        done = (flags & (EO.TERMINATED | EO.TRUNCATED)) != 0
-        self.count += done
-        self.sum_return += np.where(done, self.ret, 0.0)
-        self.sum_length += np.where(done, self.length, 0)
-        self.length[done] = 0
-        self.ret[done] = 0.0
+            term_sum = term_sum + terms[:, d]
+        flags, reward, done, length = EO.tally_step(p, self, cause_env, term_sum)
         self.h_min_episode[done] = np.inf
         if done.any():
             self._reset_envs(done)

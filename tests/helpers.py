@@ -189,12 +189,12 @@ def parent_library_flights(module, func, tmp_path):
 
 
 def assert_same_bits(ref, flights):
-    """every array of flights equals ref's of the same name bit for bit (float32 / float64 / integer arrays)"""
+    """every array of flights equals ref's of the same name bit for bit (float16 / float32 / float64 / integer arrays)"""
     assert sorted(ref.files if hasattr(ref, "files") else ref) == sorted(flights)
     for k, v in flights.items():
         r = ref[k]
         assert r.dtype == v.dtype and r.shape == v.shape, k
-        view = {4: np.uint32, 8: np.uint64}[v.dtype.itemsize]
+        view = {2: np.uint16, 4: np.uint32, 8: np.uint64}[v.dtype.itemsize]
         differ = np.ascontiguousarray(r).view(view) != np.ascontiguousarray(v).view(view)
         print("%s: %d values, %d differ from the parent library's" % (k, v.size, differ.sum()))
         assert not differ.any(), k

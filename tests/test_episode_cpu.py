@@ -4,12 +4,14 @@ import ctypes as C
 import os
 import shutil
 import subprocess
+import types
 
 import numpy as np
 import pytest
 
 from multidronesim_amd import _capi as capi
 from tests import episode_cases as EC
+from tests import episode_oracle as EO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEAR = 1e-4            # a decision with a smaller margin may go the other way in a lower precision
@@ -80,6 +82,70 @@ def test_rule_header_matches_the_oracle(rule_program, tmp_path, E, D):
         np.testing.assert_allclose(reward32[clear], r["reward"][clear], rtol=1e-5, atol=1e-5 * D, err_msg=name)
         compared += int((r["flags"][clear] & 3 != 0).sum())
     assert compared >= 20 * len(EC.RULES)
+
+
+TALLY_K, TALLY_E, TALLY_PENALTY = 12, 8, 0.3          # (0.3: not a float32 number, so the f32 replay has a rounded penalty to match)
+
+
+def tally_inputs():
+    """cause words and term sums [K, E] of the counter test, one column per situation (steps counted from 0):
+       0  never a cause: length runs on, or truncates every max_steps steps
+       1  a cause on step 2 and again on step 5: with max_steps 3 each falls on the step that would also truncate
+       2  causes on steps 4 and 5: two terminations in a row
+       3  a cause on step 3: with max_steps 3 a truncation and a termination in a row
+       4  a NaN term sum on step 1, a cause on step 7: the NaN reaches ret, then sum_return
+       5  a NaN term sum on the terminating step 6: NaN less the penalty
+       6  several cause bits at once on steps 0 and 9 (bits 0 and 5, bits 6 and 7)
+       7  never a cause, other sums"""
+    K, E = TALLY_K, TALLY_E
+    cause = np.zeros((K, E), dtype=np.int64)
+    cause[[2, 5], 1] = 4
+    cause[[4, 5], 2] = 2
+    cause[3, 3] = 16
+    cause[7, 4] = 8
+    cause[6, 5] = 2
+    cause[0, 6], cause[9, 6] = 0x21, 0xC0
+    sums = np.random.default_rng(11).uniform(0.0, 6.0, size=(K, E))
+    sums[1, 4] = sums[6, 5] = np.nan
+    return cause, sums
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("max_steps", [0, 1, 3])
+def test_env_step_carries_the_counters_like_the_oracle(rule_program, tmp_path, max_steps, prec):
+    """mds_episode.hpp episode_env_step on the host (g++, ASan + UBSan, a program of its own) carrying an EpisodeTally over 12 steps of 8
+    envs from zeroed counters, against tests/episode_oracle.py tally_step -- the EpisodeOracle's own counter lines -- replayed in the same
+    precision (np.float64 / np.float32): every step's flags and reward and the five final counters are equal exactly (a NaN equal to a NaN)."""
+    K, E = TALLY_K, TALLY_E
+    cause, sums = tally_inputs()
+    ft = {"f64": np.float64, "f32": np.float32}[prec]
+    t = types.SimpleNamespace(length=np.zeros(E, dtype=np.int64), count=np.zeros(E, dtype=np.int64), sum_length=np.zeros(E, dtype=np.int64),
+                              ret=np.zeros(E, dtype=ft), sum_return=np.zeros(E, dtype=ft))
+    params = dict(max_steps=max_steps, term_penalty=TALLY_PENALTY)
+    steps = [EO.tally_step(params, t, cause[k], sums[k].astype(ft)) for k in range(K)]
+    flags, reward, done, length = (np.stack([s[j] for s in steps]) for j in range(4))
+    assert reward.dtype == ft
+    # the situations the inputs are there for
+    term, trunc = (flags & 1) != 0, (flags & 2) != 0
+    assert not (term & trunc).any() and (done == (term | trunc)).all() and (flags >> 8 == cause).all()
+    assert (trunc[:, 0] == ((np.arange(K) + 1) % max_steps == 0 if max_steps else np.zeros(K, dtype=bool))).all()
+    assert term[2, 1] and term[5, 1] and (length[[2, 5], 1] == max_steps).all() if max_steps == 3 else term[2, 1]
+    assert done[4, 2] and done[5, 2] and length[5, 2] == 1
+    assert (trunc[2, 3] and term[3, 3]) if max_steps == 3 else term[3, 3]
+    assert np.isnan(reward[1, 4]) and not np.isnan(reward[2, 4]) and np.isnan(t.sum_return[4]) and np.isnan(reward[6, 5]) and np.isnan(t.sum_return[5])
+    assert not np.isnan(t.sum_return[[0, 1, 2, 3, 6, 7]]).any()
+    fin, fout = str(tmp_path / "tally.in"), str(tmp_path / "tally.out")
+    np.concatenate([np.array([K, E, max_steps, TALLY_PENALTY]), cause.astype(np.float64).reshape(-1), sums.reshape(-1)]).tofile(fin)
+    ran = subprocess.run([rule_program, fin, fout, prec, "tally"], capture_output=True, text=True)
+    assert ran.returncode == 0, (ran.returncode, ran.stderr[-2000:])
+    out = np.fromfile(fout, dtype=np.float64)
+    assert out.size == 2 * K * E + 5 * E
+    np.testing.assert_array_equal(out[:K * E].astype(np.int64).reshape(K, E), flags)
+    np.testing.assert_array_equal(out[K * E:2 * K * E].reshape(K, E), reward.astype(np.float64))
+    got = out[2 * K * E:].reshape(5, E)
+    for row, name in enumerate(("length", "count", "sum_length", "ret", "sum_return")):
+        np.testing.assert_array_equal(got[row], getattr(t, name).astype(np.float64), err_msg=name)
+    assert t.count.sum() > 0 and (t.sum_length + t.length == K).all()
 
 
 @pytest.fixture(scope="module")
