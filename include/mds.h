@@ -404,6 +404,66 @@ int mds_episode_policy_compute(mds_handle* h, const void* obs_dev, void* rpm_dev
 int mds_rollout_episodes_policy(mds_handle* h, int first_step, int n_steps, void* obs_log_dev, int log_slots, void* action_log_dev,
                                 void* reward_log_dev, int32_t* flags_log_dev, int steps_per_launch, void* obs_dev, void* stream);
 
+/* GAUSSIAN ACTIONS DRAWN IN THE ROLLOUT KERNEL (the arithmetic, stated once: multidronesim_amd/csrc/mds_policy_noise.hpp): what an
+ * on-policy learner (PPO, A2C) collects.  The action distribution is stable-baselines3's DiagGaussianDistribution with a
+ * state-independent log_std: a ~ N(y, diag(sigma^2)), y the network's output, sigma = exp(log_std).  The four standard normals of one
+ * drone at one step are a PURE FUNCTION of
+ *   (seed, g, ordinal, length, epoch):   g = first_env * D + i, the drone's index in the whole env set;
+ *                                        ordinal = the env's `count` (mds_episode_ptrs ptrs[2], read as uint32) when the action is formed;
+ *                                        length = the env's running-episode `length` (ptrs[0]) at that moment: before the step's
+ *                                                 increment, 0 for the first step of an episode;
+ *                                        epoch = 0 after mds_set_episode_policy_noise, + 1 with every host call that restarts every
+ *                                                env's running episode: mds_reset, mds_reset_async, mds_reset_episodes, and
+ *                                                mds_set_episodes with parameters (else a reset that keeps or zeroes `count` would
+ *                                                replay the same noise),
+ * namely Philox4x32-10 with key (seed low word, seed high word) -- the noise's own seed -- on the counter (g, ordinal, 3 + length,
+ * epoch), the sum mod 2^32.  Word 2 starts at 3: even with the seed of the randomised starts and epoch == generation no block
+ * coincides with a start draw's b = 0, 1, 2.  One block per drone-step; (w0, w1) give eps[0], eps[1] and (w2, w3) give eps[2], eps[3]
+ * by Box-Muller: u = (2 (w_a >> 9) + 1) 2^-24 (never 0 or 1, the same 24-bit value in every compute type), r = sqrt(-2 ln u) <= 5.77,
+ * theta = pi * s(w_b) with the s of the randomised starts, eps = r cos(theta), r sin(theta).  So a draw depends neither on
+ * steps_per_launch, nor on the thread mapping, nor on how the env set is sharded over handles.
+ *   sample   a[j] = y[j] + sigma[j] eps[j] (one fma)          commanded RPM   rpm_base + rpm_scale * clamp(a[j], -1, 1): the clamp
+ *   logp     -(0.5 sum_j eps[j]^2) - (sum_j log_std[j] + 2 ln(2 pi))           acts on the sample, as SB3 clips a sampled action
+ * logp is Normal(y, sigma).log_prob(a).sum(-1) of the UNCLIPPED sample (SB3's convention), formed from eps, never from (a - y) / sigma. */
+typedef struct mds_episode_policy_noise {
+  uint64_t seed;
+  int64_t  first_env;     /* global index of this handle's env 0, as in mds_episode_randomisation */
+  double   log_std[4];
+} mds_episode_policy_noise;
+/* Configures (params NULL: switches off) the noise and sets epoch to 0; touches no state and no counter.  MDS_EINVAL for a log_std
+ * that is not finite or whose exp is 0 (a denormal counts as 0) or infinite in the compute type, first_env < 0, or (first_env + E) * D beyond uint32;
+ * MDS_ESTATE without a policy (mds_set_episode_policy).  mds_set_episodes(h, NULL, ..) and switching the policy off switch the noise
+ * off too; a re-upload of the policy's weights keeps it (a learner re-uploads every iteration), and so does a re-configuration of the
+ * episode parameters, the collision causes or the randomisation.  A failed call leaves the handle as it was.  Only
+ * mds_rollout_episodes_sampled and mds_episode_policy_sample read the noise: mds_rollout_episodes_policy on a handle with noise
+ * configured remains the deterministic (evaluation) rollout, bit for bit.  epoch is host bookkeeping passed by value: a captured
+ * call bakes it in, as with generation. */
+int mds_set_episode_policy_noise(mds_handle* h, const mds_episode_policy_noise* params, void* stream);
+typedef struct mds_episode_sample_rings {   /* each may be NULL; [log_slots, ...]; storage type unless stated */
+  void *acted_obs;   /* [.., n, 20] the rows the action of step j was drawn on (post-reset where the env was just done) */
+  void *obs;         /* [.., n, 20] the transition's result, before any reset (as obs_log_dev)                          */
+  void *action;      /* [.., n, 4]  commanded RPM   */
+  void *sample;      /* [.., n, 4]  a, before the clamp */
+  void *logp;        /* [.., n]     compute type    */
+  void *reward;      /* [.., E]     compute type    */
+  int32_t *flags;    /* [.., E]                      */
+} mds_episode_sample_rings;
+/* mds_rollout_episodes_policy's loop with the commanded mean replaced by a sample drawn in the kernel, between the network and the
+ * step.  Slot j % log_slots of every ring given receives step j = first_step + k; rings NULL is no ring.  acted_obs[j] holds the bits
+ * obs_dev would have received had the call ended before step j: with sample and logp it is the (s_t, a_t, log pi(a_t | s_t)) a learner
+ * pairs, also across a reset with randomised starts.  (The RPM echo columns of a call's first step are those of the step before it
+ * where the handle tracked them -- always under DYN_DRAG or after another sampled call -- else NaN, as in mds_get_obs.)  The other
+ * rings, the collision causes, the randomised starts and obs_dev mean what they mean in mds_rollout_episodes_policy.
+ * steps_per_launch changes no bit.  MDS_EALIGN for a ring that is not 16-byte aligned; MDS_ESTATE without a policy or without noise.
+ * Only enqueues, on the caller's stream. */
+int mds_rollout_episodes_sampled(mds_handle* h, int first_step, int n_steps, const mds_episode_sample_rings* rings, int log_slots,
+                                 int steps_per_launch, void* obs_dev, void* stream);
+/* The policy and the draw alone, on caller-supplied observation rows obs_dev [n,20] -> rpm_dev [n,4], sample_dev [n,4] (storage type)
+ * and logp_dev [n] (compute type), the last two or NULL.  The env's count and length are read from the handle's device counters:
+ * called on the current observation and followed by mds_step_episodes it draws exactly what mds_rollout_episodes_sampled draws at its
+ * next step.  MDS_ESTATE without a policy or without noise.  Only enqueues. */
+int mds_episode_policy_sample(mds_handle* h, const void* obs_dev, void* rpm_dev, void* sample_dev /*or NULL*/, void* logp_dev /*or NULL*/, void* stream);
+
 /* How mds_rollout_geometric / mds_rollout_step / mds_rollout_cbf_geometric issue their steps.  Drones never read each
  * other's rows in the fused step (and a barrier row couples drones of one env only), so the two halves of the shard are
  * independent step chains: on two internal streams one half's load/store bursts fill the other's compute phase, and the

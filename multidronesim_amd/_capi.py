@@ -62,6 +62,14 @@ class MdsEpisodePolicy(C.Structure):
                 ("rpm_base", C.c_double), ("rpm_scale", C.c_double)]
 
 
+class MdsEpisodePolicyNoise(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_env", C.c_int64), ("log_std", C.c_double * 4)]
+
+
+class MdsEpisodeSampleRings(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("acted_obs", "obs", "action", "sample", "logp", "reward", "flags")]
+
+
 POLICY_IN, POLICY_OUT, POLICY_MAX_WIDTH = 12, 4, 64
 
 
@@ -127,6 +135,9 @@ PROTOTYPES = {
     "mds_set_episode_policy": (C.c_int, [_P, C.POINTER(MdsEpisodePolicy), _PD, _P]),
     "mds_episode_policy_compute": (C.c_int, [_P, _P, _P, _P]),
     "mds_rollout_episodes_policy": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "mds_set_episode_policy_noise": (C.c_int, [_P, C.POINTER(MdsEpisodePolicyNoise), _P]),
+    "mds_rollout_episodes_sampled": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MdsEpisodeSampleRings), C.c_int, C.c_int, _P, _P]),
+    "mds_episode_policy_sample": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "mds_rollout_geometric_fused": (C.c_int, [_P, C.c_double, C.c_int, _P, _P, _P]),
     "mds_lemniscate_eval": (C.c_int, [_P, C.c_double, _P, _P]),
     "mds_geometric_compute": (C.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -1,6 +1,7 @@
 // C-ABI of libmds (include/mds.h): handle management, constant set-up in double, dtype
 // dispatch and kernel launches.  No torch types, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -22,6 +23,7 @@
 #if MDS_PART & 1
 #include "mds_episode_kernels.hip"  // per-env episodes inside the rollout kernel (part 1 only)
 #include "mds_episode_policy_kernels.hip"   // ... driven by an MLP policy evaluated in the kernel (part 1 only)
+#include "mds_episode_sample_kernels.hip"   // ... whose actions are drawn from a Gaussian around its output (part 1 only)
 #endif
 #if MDS_PART & 2
 #include "mds_cbf_kernels.hip"      // (part 2 only: it defines a non-template kernel)
@@ -245,6 +247,11 @@ struct mds_handle {
   mds_episode_policy ep_pol = {};
   int ep_policy_width = 0;
   void* ep_policy_w = nullptr;
+  // the Gaussian noise of the policy's actions (mds_set_episode_policy_noise) and the epoch word of its draw: 0 at configuration, + 1
+  // with every host call that restarts every env's running episode
+  bool ep_noise = false;
+  mds_episode_policy_noise ep_noise_p = {};
+  uint32_t ep_epoch = 0;
 };
 
 template <typename T> static inline const HostParams<T>& params(const mds_handle* h) {
@@ -525,6 +532,13 @@ template <typename T> static EpisodeLaunch<T> episode_launch(const mds_handle* h
 template <typename T> static EpisodePolicy<T> episode_policy_args(const mds_handle* h) {
   return {(const T*)h->ep_policy_w, h->ep_pol.n_hidden, h->ep_pol.activation, (T)h->ep_pol.rpm_base, (T)h->ep_pol.rpm_scale};
 }
+// the handle's action noise as the kernels take it
+template <typename T> static PolicyNoise<T> episode_noise_args(const mds_handle* h) {
+  const mds_episode_policy_noise& p = h->ep_noise_p;
+  PolicyNoise<T> a;
+  fill_policy_noise<T>(p.seed, (uint32_t)((unsigned long long)p.first_env * (unsigned long long)h->cfg.num_drones), h->ep_epoch, p.log_std, a);
+  return a;
+}
 // the two dtypes the policy kernels are built for (mds_set_episode_policy has refused the others)
 template <typename F> static void with_policy_dtype(int dtype, F&& f) {
   if (dtype == MDS_F64) f(DType<double, double>{});
@@ -743,7 +757,9 @@ static int episode_hmin_clear(mds_handle* h, hipStream_t st, void* block, int fi
 // the running episode of every env starts anew (length, return, smallest h); the statistics of the completed ones stay
 static int episode_restart(mds_handle* h, hipStream_t st) {
   MDS_HIP(hipMemsetAsync(h->ep_counters, 0, 2 * h->ep_slots * 8, st));
-  if (h->ep_hmin) return episode_hmin_clear(h, st, h->ep_hmin, 1, 1);
+  if (h->ep_hmin)
+    if (int rc = episode_hmin_clear(h, st, h->ep_hmin, 1, 1)) return rc;
+  ++h->ep_epoch;                       // (mds_policy_noise.hpp: the same count and length must not replay the same noise; a failed restart moves nothing)
   return MDS_OK;
 }
 
@@ -1363,7 +1379,7 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_set_episodes: null handle");
   if (!p) {
-    h->ep_on = h->ep_safe = h->ep_random = h->ep_policy = false;
+    h->ep_on = h->ep_safe = h->ep_random = h->ep_policy = h->ep_noise = false;
     return MDS_OK;
   }
   if (p->max_steps < 0 || !(p->reward_r0 == p->reward_r0) || !(p->term_penalty == p->term_penalty))
@@ -1388,6 +1404,7 @@ int mds_set_episodes(mds_handle* h, const mds_episode_params* p, const double* t
   if (h->ep_hmin)                      // the running episodes start anew: so do their minima (the safety settings themselves stay)
     if (int rc = episode_hmin_clear(h, st, h->ep_hmin, 1, 1)) return rc;
   h->ep_on = true;
+  ++h->ep_epoch;                       // every env's running episode starts anew
   if (target_host) MDS_HIP(hipStreamSynchronize(st));   // host buffer may be reused by the caller
   return MDS_OK;
 }
@@ -1531,7 +1548,7 @@ int mds_set_episode_policy(mds_handle* h, const mds_episode_policy* p, const dou
   MDS_DEV(h);
   if (!h) return fail(MDS_EINVAL, "mds_set_episode_policy: null handle");
   if (!p) {
-    h->ep_policy = false;
+    h->ep_policy = h->ep_noise = false;
     return MDS_OK;
   }
   auto finite = [](double x) { return x > -(double)INFINITY && x < (double)INFINITY; };
@@ -1620,6 +1637,105 @@ int mds_rollout_episodes_policy(mds_handle* h, int first_step, int n_steps, void
         });
       });
     }, rk4, drag);
+  }
+  return check_launches();
+}
+
+// ---- Gaussian actions drawn in the rollout kernel (mds_policy_noise.hpp, mds_episode_sample_kernels.hip) ----
+static_assert(sizeof(mds_episode_policy_noise) == 48, "include/mds.h mds_episode_policy_noise: a uint64, an int64 and four doubles");
+static_assert(sizeof(mds_episode_sample_rings) == 7 * sizeof(void*), "include/mds.h mds_episode_sample_rings: seven pointers");
+
+int mds_set_episode_policy_noise(mds_handle* h, const mds_episode_policy_noise* p, void* stream) {
+  (void)stream;                        // (nothing is enqueued: the parameters travel with the launches)
+  if (!h) return fail(MDS_EINVAL, "mds_set_episode_policy_noise: null handle");
+  if (!p) {
+    h->ep_noise = false;
+    return MDS_OK;
+  }
+  // sigma must be a normal number of the compute type (compared in double, nothing out of range is converted; a denormal counts as 0:
+  // the device may flush it)
+  const bool f64 = h->cfg.dtype == MDS_F64;
+  const double lo = f64 ? DBL_MIN : (double)FLT_MIN, hi = f64 ? DBL_MAX : (double)FLT_MAX;
+  for (int j = 0; j < 4; ++j) {
+    const double ls = p->log_std[j], sd = exp(ls);
+    if (!(ls > -(double)INFINITY && ls < (double)INFINITY) || !(sd >= lo && sd <= hi))
+      return fail(MDS_EINVAL, "mds_set_episode_policy_noise: a log_std is not finite, or its exp is 0 or infinite in the compute type");
+  }
+  // g = first_env * D + i is a 32-bit counter word: the whole shard must fit
+  const unsigned long long E = (unsigned long long)h->cfg.num_envs, D = (unsigned long long)h->cfg.num_drones;
+  if (p->first_env < 0 || (unsigned long long)p->first_env > 0xFFFFFFFFull || ((unsigned long long)p->first_env + E) * D > 0xFFFFFFFFull)
+    return fail(MDS_EINVAL, "mds_set_episode_policy_noise: first_env < 0, or (first_env + num_envs) * num_drones does not fit 32 bits");
+  if (!h->ep_on || !h->ep_policy) return fail(MDS_ESTATE, "mds_set_episode_policy_noise: no policy configured (mds_set_episodes, mds_set_episode_policy)");
+  h->ep_noise_p = *p;
+  h->ep_epoch = 0;
+  h->ep_noise = true;
+  return MDS_OK;
+}
+
+int mds_episode_policy_sample(mds_handle* h, const void* obs, void* rpm, void* sample, void* logp, void* stream) {
+  MDS_DEV(h);
+  if (!h || !obs || !rpm) return fail(MDS_EINVAL, "mds_episode_policy_sample: null argument");
+  if (!aligned16(obs) || !aligned16(rpm) || !aligned16(sample) || !aligned16(logp))
+    return fail(MDS_EALIGN, "mds_episode_policy_sample: obs_dev/rpm_dev/sample_dev/logp_dev");
+  if (!h->ep_on || !h->ep_policy || !h->ep_noise)
+    return fail(MDS_ESTATE, "mds_episode_policy_sample: no policy noise configured (mds_set_episode_policy, mds_set_episode_policy_noise)");
+  hipStream_t st = (hipStream_t)stream;
+  const char* cb = (const char*)h->ep_counters;
+  const size_t sl = h->ep_slots * 8;
+  with_policy_dtype(h->cfg.dtype, [&](auto DT) {
+    using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+    with_int<32, 64>(h->ep_policy_width, [&](auto W) {
+      k_episode_policy_sample<T, S, W()><<<grid_for(h->n, kBlock), kBlock, 0, st>>>(
+          h->n, h->ld, h->cfg.num_drones, (const T*)h->origin, (const T*)h->ep_target, episode_policy_args<T>(h), episode_noise_args<T>(h),
+          (const int*)(cb + 2 * sl), (const int*)cb, (const S*)obs, (S*)rpm, (S*)sample, (T*)logp);
+    });
+  });
+  return check_launches();
+}
+
+int mds_rollout_episodes_sampled(mds_handle* h, int first_step, int n_steps, const mds_episode_sample_rings* rings, int log_slots,
+                                 int steps_per_launch, void* obs, void* stream) {
+  MDS_DEV(h);
+  if (!h) return fail(MDS_EINVAL, "mds_rollout_episodes_sampled: null handle");
+  const mds_episode_sample_rings none = {};
+  const mds_episode_sample_rings& R = rings ? *rings : none;
+  const bool ring = R.acted_obs || R.obs || R.action || R.sample || R.logp || R.reward || R.flags;
+  if (steps_per_launch < 1 || first_step < 0 || n_steps < 0 || (ring && log_slots < 1)) return fail(MDS_EINVAL, "mds_rollout_episodes_sampled: arguments");
+  if (!aligned16(obs) || !aligned16(R.acted_obs) || !aligned16(R.obs) || !aligned16(R.action) || !aligned16(R.sample) || !aligned16(R.logp) ||
+      !aligned16(R.reward) || !aligned16(R.flags))
+    return fail(MDS_EALIGN, "mds_rollout_episodes_sampled: obs_dev or a ring");
+  if (!h->ep_on || !h->ep_policy || !h->ep_noise)
+    return fail(MDS_ESTATE, "mds_rollout_episodes_sampled: no policy noise configured (mds_set_episode_policy, mds_set_episode_policy_noise)");
+  hipStream_t st = (hipStream_t)stream;
+  const bool rk4 = h->cfg.integrator == MDS_INTEGRATOR_RK4, drag = has_drag(h);
+  for (Chunks c{n_steps, steps_per_launch, 0.0, 0.0, ring ? first_step % log_slots : 0, ring ? log_slots : 0}; c.k < n_steps; c.advance(c.len())) {
+    const int ks = c.len(), s0 = c.slot;
+    const bool last = c.k + ks == n_steps;
+    // the RPM planes carry the echo from launch to launch (the acted-on rows of a launch's first step read it): NaN where they are
+    // not current (what mds_get_obs reports then), always written -- which makes them current
+    if (!h->track_rpm && h->rpm_stale) {
+      const size_t count = 4 * h->ld;
+      with_policy_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T;
+        k_episode_echo_unknown<T><<<dim3((unsigned)((count + kBlock - 1) / kBlock)), kBlock, 0, st>>>(count, (T*)h->last_rpm);
+      });
+    }
+    with_flags([&](auto RK4, auto DRAG) {
+      with_policy_dtype(h->cfg.dtype, [&](auto DT) {
+        using T = typename decltype(DT)::T; using S = typename decltype(DT)::S;
+        const EpisodeLaunch<T> ep = episode_launch<T>(h);
+        const EpisodeSampleRings<T, S> rg = {(S*)R.acted_obs, (S*)R.obs, (S*)R.action, (S*)R.sample, (T*)R.logp, (T*)R.reward, (int*)R.flags};
+        with_int<32, 64>(h->ep_policy_width, [&](auto W) {
+          // (float64, RK4, 32 wide is not built, as in mds_rollout_episodes_policy: mds_set_episode_policy pads such a handle's policy to 64)
+          if constexpr (!(RK4() && sizeof(T) == 8 && W() == 32))
+          k_rollout_episodes_sampled<T, S, RK4(), DRAG(), W()><<<ep.grid, kBlock, 0, st>>>(
+              params<T>(h).c, ep.rule, h->n, h->ld, ep.D, ep.epb, (S*)h->state, (const S*)h->ep_image, (const T*)h->origin, (const T*)h->ep_target,
+              (T*)h->last_rpm, episode_policy_args<T>(h), episode_noise_args<T>(h), rg, s0, ring ? log_slots : 1, ks,
+              (S*)(last ? obs : nullptr), ep.cnt, h->ep_safe ? 1 : 0, ep.safe, h->ep_random ? 1 : 0, ep.rnd);
+        });
+      });
+    }, rk4, drag);
+    h->rpm_stale = false;
   }
   return check_launches();
 }

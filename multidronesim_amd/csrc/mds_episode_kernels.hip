@@ -20,11 +20,12 @@
 // stands in the kernel).  LDS of the sibling: observation staging + 5 words (cause, term, h) + 3 position and 3 origin words per lane
 // = 58 368 B in float64, 29 696 B in float32, 19 456 B with fp16 storage.
 //
-// Shared and written out.  The two kernels here and k_rollout_episodes_policy (mds_episode_policy_kernels.hip) share the lane map
+// Shared and written out.  The two kernels here, k_rollout_episodes_policy (mds_episode_policy_kernels.hip) and
+// k_rollout_episodes_sampled (mds_episode_sample_kernels.hip) share the lane map
 // (EpisodeLane) and the type of the env's counters (mds_episode.hpp EpisodeTally); the env's step is stated for the host in
 // mds_episode.hpp episode_env_step, and each kernel's loop writes the same lines out.  Why: these kernels keep the instruction order
 // they had, the only one measured to be as fast, and any function over the tally or the counters changes it, as does one body under
-// a SAFE flag (profiles/asm_equiv_episode_pieces.md, asm_equiv_episode_safety.md).  A change to one loop is a change to all three.
+// a SAFE flag (profiles/asm_equiv_episode_pieces.md, asm_equiv_episode_safety.md).  A change to one loop is a change to all four.
 #include "mds_episode.hpp"
 #include "mds_episode_random.hpp"
 

@@ -76,6 +76,8 @@ MDS_HD float m_rint(float x) { return rintf(x); }
 MDS_HD double m_rint(double x) { return rint(x); }
 MDS_HD float m_exp(float x) { return expf(x); }
 MDS_HD double m_exp(double x) { return exp(x); }
+MDS_HD float m_log(float x) { return logf(x); }
+MDS_HD double m_log(double x) { return log(x); }
 MDS_HD float m_abs(float x) { return fabsf(x); }
 MDS_HD double m_abs(double x) { return fabs(x); }
 MDS_HD double m_atan2(double y, double x) { return atan2(y, x); }

@@ -655,6 +655,72 @@ class BaseAviary:
         self.step_counter += n_steps * self.PYB_STEPS_PER_CTRL
         return self._obs
 
+    # ------------------------------------------------------------------ Gaussian actions drawn in the rollout kernel
+    def set_episode_policy_noise(self, log_std, seed: int = 0, first_env: int = 0, enabled: bool = True):
+        """Gaussian exploration noise of the policy's actions (mds_set_episode_policy_noise; needs ``set_episode_policy`` first):
+        ``rollout_episodes_sampled`` and ``episode_policy_sample`` command ``clip(a)`` with ``a ~ N(y, diag(exp(log_std))^2)``, ``y`` the
+        network's output and ``log_std`` the state-independent vector of stable-baselines3's ``DiagGaussianDistribution`` (a scalar or
+        4 values).  A draw is a pure function of (``seed``, the drone's global index ``first_env * D + i``, the env's ``count`` of
+        completed episodes, the running episode's ``length``, the number of resets of all envs since this call): it does not depend on
+        ``steps_per_launch`` or on how the envs are sharded.  ``rollout_episodes_policy`` stays the deterministic rollout.
+        ``enabled=False`` switches the noise off; so does switching off the policy or the episodes."""
+        self._require_open()
+        if not enabled:
+            capi.check(self._lib.mds_set_episode_policy_noise(self._h, None, self._stream()), "mds_set_episode_policy_noise")
+            return
+        if isinstance(log_std, torch.Tensor):
+            log_std = log_std.detach().double().cpu().numpy()
+        p = capi.MdsEpisodePolicyNoise()
+        p.seed, p.first_env = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_env)
+        p.log_std = (C.c_double * 4)(*np.broadcast_to(np.asarray(log_std, dtype=np.float64).reshape(-1), (4,)))
+        capi.check(self._lib.mds_set_episode_policy_noise(self._h, C.byref(p), self._stream()), "mds_set_episode_policy_noise")
+
+    def episode_policy_sample(self, obs: torch.Tensor):
+        """The policy and one draw on observation rows ``obs`` [E,D,20] (mds_episode_policy_sample): ``(rpm [E,D,4], sample [E,D,4],
+        logp [E,D])``, new tensors -- the commanded RPM, the sample before the clamp and its log-probability (float32; float64 on a
+        float64 env).  The draw is the one of each env's current ``count`` and ``length``: on the current observation and followed by
+        ``step_episodes`` this is the policy-in-the-loop form of ``rollout_episodes_sampled``."""
+        self._require_open()
+        if obs.dtype != self.dtype or not obs.is_contiguous() or obs.numel() != self.n * capi.OBS_DIM or obs.device != self._obs.device:
+            raise ValueError("obs must be a contiguous [E,D,20] device tensor of the env's dtype")
+        rpm = torch.empty((self.NUM_ENVS, self.NUM_DRONES, capi.ACT_DIM), dtype=self.dtype, device=self._obs.device)
+        sample = torch.empty_like(rpm)
+        logp = torch.empty((self.NUM_ENVS, self.NUM_DRONES), dtype=self._episode_dtype(), device=self._obs.device)
+        capi.check(self._lib.mds_episode_policy_sample(self._h, C.c_void_p(obs.data_ptr()), C.c_void_p(rpm.data_ptr()), C.c_void_p(sample.data_ptr()),
+                                                       C.c_void_p(logp.data_ptr()), self._stream()),
+                   "mds_episode_policy_sample")
+        return rpm, sample, logp
+
+    def rollout_episodes_sampled(self, first_step: int, n_steps: int, acted_obs_log: torch.Tensor | None = None, obs_log: torch.Tensor | None = None,
+                                 action_log: torch.Tensor | None = None, sample_log: torch.Tensor | None = None, logp_log: torch.Tensor | None = None,
+                                 reward_log: torch.Tensor | None = None, flags_log: torch.Tensor | None = None, steps_per_launch: int = 1):
+        """``n_steps`` control steps of the configured policy with actions drawn in the kernel (mds_rollout_episodes_sampled), as
+        ``rollout_episodes_policy`` otherwise.  Step j writes slot ``j % T`` of each log given: ``acted_obs_log`` [T,E,D,20] (the rows
+        the action was drawn on: post-reset where the env was just done), ``obs_log`` [T,E,D,20] (the transition's rows, before any
+        reset), ``action_log`` [T,E,D,4] (the commanded RPM), ``sample_log`` [T,E,D,4] (the sample before the clamp), ``logp_log``
+        [T,E,D] (float32; float64 on a float64 env), ``reward_log`` [T,E], ``flags_log`` [T,E] int32.  Returns the current observation."""
+        self._require_open()
+        slots = set()
+        n, E, rdt = self.n, self.NUM_ENVS, self._episode_dtype()
+        logs = (("acted_obs_log", acted_obs_log, self.dtype, n * capi.OBS_DIM), ("obs_log", obs_log, self.dtype, n * capi.OBS_DIM),
+                ("action_log", action_log, self.dtype, n * capi.ACT_DIM), ("sample_log", sample_log, self.dtype, n * capi.ACT_DIM),
+                ("logp_log", logp_log, rdt, n), ("reward_log", reward_log, rdt, E), ("flags_log", flags_log, torch.int32, E))
+        for name, log, dt, per in logs:
+            if log is None:
+                continue
+            if log.dtype != dt or not log.is_contiguous() or log.numel() == 0 or log.numel() % per:
+                raise ValueError(f"{name} must be a contiguous tensor of dtype {dt} with {per} values per step")
+            slots.add(log.numel() // per)
+        if len(slots) > 1:
+            raise ValueError("the logs must hold the same number of steps")
+        rings = capi.MdsEpisodeSampleRings(*(log.data_ptr() if log is not None else None for _, log, _, _ in logs))
+        capi.check(self._lib.mds_rollout_episodes_sampled(self._h, C.c_int(int(first_step)), C.c_int(int(n_steps)), C.byref(rings),
+                                                          C.c_int(slots.pop() if slots else 0), C.c_int(int(steps_per_launch)),
+                                                          C.c_void_p(self._obs.data_ptr()), self._stream()),
+                   "mds_rollout_episodes_sampled")
+        self.step_counter += n_steps * self.PYB_STEPS_PER_CTRL
+        return self._obs
+
     def set_rollout_streams(self, n_streams: int = 0):
         """How rollout_geometric issues its steps: 0 auto, 1 the current stream only, 2 the two halves of the shard on two
         internal streams (mds_set_rollout_streams).  Same results either way."""
